@@ -1,7 +1,12 @@
 """Headline benchmark: Msamples/s of the path-integrator hot path on the Cornell box,
 1920x1080 @ 512 spp, diffuse BSDFs (BASELINE.json configs[1]), N GPUs of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--width --height --spp]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--width --height --spp] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds what takes runs or time of its own: the
+CPU baseline, the live PMC passes, the parity digest of the timed film and the `extras` block (the other BASELINE
+configurations); without it those fields are null. `--dump-outputs DIR` writes what the last timed step computed (the
+film, float32, and its sample / segment counts) as DIR/<name>.npy after the timed steps.
 
 A "step" is one complete render of the workload (scene + BVH already resident in
 HBM; the timed region is mi_render + the film reduce). N > 1 = one rank per GPU: either launched under
@@ -13,7 +18,7 @@ the step. `--shard passes` (never chosen automatically) renders the reference's
 samples_per_pass = spp / N job instead, one pass per rank; the JSON line names the
 partition in `shard` and `config.parallelism`.
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`
-(dominant kernel, HIP-event timed inside the library on its own stream) and
+(dominant kernel, HIP-event timed inside the library on its own stream) and, with --full,
 `cpu_baseline` (the scalar_rgb oracle on the host cores, bounded sample).
 """
 import argparse
@@ -305,6 +310,27 @@ def reduce_label(backend):
 
 REDUCE_HOW = {0: "none (one context)", 1: "device add, rank order (contexts share a GPU, or RCCL unavailable)", 2: "RCCL ncclReduce (mi_film_reduce)"}
 
+DUMP_FILM_MAX_BYTES = 60 << 20      # the whole film up to this size (1080p: 41.5 MB); above it a fixed sample of its pixels
+
+
+def dump_outputs(out_dir, film, samples, segments):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, for comparing two builds output for output — the float32 film
+    (H x W x 5: RGB, alpha, weight) as film.npy and its [samples, segments] as counts.npy (float64). A film larger than
+    DUMP_FILM_MAX_BYTES is written as film_sample.npy (the pixels chosen by a fixed seed, in index order) next to
+    film_sample_index.npy (their flat pixel indices, float64)."""
+    import numpy as np
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if film.nbytes <= DUMP_FILM_MAX_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), film)
+    else:
+        px = film.reshape(-1, film.shape[-1])
+        keep = DUMP_FILM_MAX_BYTES // px[0].nbytes
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=keep, replace=False))
+        np.save(os.path.join(out_dir, "film_sample.npy"), px[idx])
+        np.save(os.path.join(out_dir, "film_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([samples, segments], dtype=np.float64))
+
 
 def native_reduce_main(args):
     """`--native-reduce`: the N-GPU frame from ONE process through the C++ host layer — Scene::build(devices) puts the scene on N
@@ -340,6 +366,8 @@ def native_reduce_main(args):
         samples += c.samples; segments += c.segments; ms_path += c.ms_path
     elapsed = time.perf_counter() - t0
     film = sensor.film.data((H, W, 5))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, film, c.samples, c.segments)
     value = float(W) * H * SPP * args.steps / elapsed / 1e6
     s_bar = segments / max(samples, 1)
     alg = 280.0 * segments + B_SPLAT * samples
@@ -368,12 +396,17 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=512)
+    ap.add_argument("--full", action="store_true", help="also measure and check what takes runs of its own: the CPU baseline, the live "
+                    "PMC passes, the parity of the timed film against the oracle's digest and the `extras` block (the --no-* switches "
+                    "below still leave single parts out); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(film.npy: the float32 film, H x W x 5; counts.npy: its samples and segments) into DIR (bench_outputs/ is git-ignored)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-counters", action="store_true", help="do not collect the dominant kernel's PMC counters in this run (four "
-                    "rocprofv3 passes over one extra frame in a child process, ~40 s; N = 1 only); roofline.traffic / .measured then come "
+    ap.add_argument("--no-live-counters", action="store_true", help="with --full: do not collect the dominant kernel's PMC counters in this run "
+                    "(four rocprofv3 passes over one extra frame in a child process, ~40 s; N = 1 only); roofline.traffic / .measured then come "
                     "from profiles/traffic.json while the kernel sources still hash to what was profiled")
     ap.add_argument("--no-extras", action="store_true", help="skip the `extras` block (the other BASELINE configurations at a few "
-                    "spp each, after the timed headline; only the default N = 1 Cornell run carries it)")
+                    "spp each, after the timed headline; only a --full N = 1 run of the default Cornell workload carries it)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for "
                     "exercising the multi-rank path on a box with fewer GPUs than ranks, together with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses GPU 0")
@@ -412,6 +445,8 @@ def main():
     ap.add_argument("--samples-per-launch", type=int, default=-1,
                     help="resident plan: samples each pixel advances per launch (-1 = all spp in one launch, 0 = library default)")
     args = ap.parse_args()
+    if args.steps < 1 and not args.dry_ranks:
+        ap.error("--steps must be at least 1")
 
     if args.native_reduce:
         return native_reduce_main(args)
@@ -530,6 +565,8 @@ def main():
         value = total_samples / elapsed / 1e6
         s_bar = agg["segments"] / max(agg["samples"], 1)
         hc = dev.counters()                      # the headline frames' counters (nothing rendered after them may leak into the line)
+        if args.dump_outputs:                    # before the extras, which render into the same film buffer
+            dump_outputs(args.dump_outputs, film.detach().cpu().numpy().reshape(H, W, 5), hc.samples, hc.segments)
         pk = hc.path_kernel
         path_kernel = "k_path_phased" if pk in (1, 3) else "k_path_resident"
         tc_name, ta_name = ("k_trace_stream", "k_sort_hits") if pk == 2 else ("k_trace<closest>", "k_trace<any>")
@@ -556,7 +593,7 @@ def main():
             # kernel sources still hash to what the profile was taken on (kernel_src_sha16); otherwise the fields stay null.
             traffic = None; measured = None
             entry = None; source = None
-            if world == 1 and not args.no_live_counters and args.shard_of <= 1 and not os.environ.get("MIW_BENCH_NO_LIVE"):
+            if args.full and world == 1 and not args.no_live_counters and args.shard_of <= 1 and not os.environ.get("MIW_BENCH_NO_LIVE"):
                 workload = ["--width", str(W), "--height", str(H), "--spp", str(SPP), "--scene", args.scene, "--tess", str(args.tess),
                             "--variant", args.variant, "--bvh-quality", str(args.bvh_quality), "--integrator", args.integrator,
                             "--plan", str(args.plan), "--film-mode", str(args.film_mode), "--samples-per-launch", str(args.samples_per_launch)]
@@ -608,7 +645,7 @@ def main():
                 "pipeline_frac": (value / world) * 1e6 * b_alg / (HBM_PEAK_GBS * 1e9),
             }
         cpu = None
-        if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle_py
             O = oracle_py.load(args.variant)
@@ -618,10 +655,10 @@ def main():
         parity = None
         headline = (world == 1 and args.scene == "cornell" and args.variant == "scalar_rgb" and args.shard_of <= 1
                     and args.integrator == "path" and (W, H, SPP) == (1920, 1080, 512) and shard != "passes")
-        if headline and args.steps > 0:
+        if args.full and headline and args.steps > 0:
             parity = film_parity(film, "c2", hc.samples, hc.segments)
         extras = None
-        if (not args.no_extras and world == 1 and args.scene == "cornell" and args.variant == "scalar_rgb" and args.shard_of <= 1
+        if (args.full and not args.no_extras and world == 1 and args.scene == "cornell" and args.variant == "scalar_rgb" and args.shard_of <= 1
                 and args.integrator == "path" and (W, H, SPP) == (1920, 1080, 512)):
             extras = run_extras(api, scenes, film, C)
         out = {

@@ -97,3 +97,34 @@ def test_a_film_that_is_not_the_oracles_makes_the_parity_field_false():
         assert bench.film_parity(flipped, "_t")["film_sha256"] != real["film_sha256"]
     finally:
         del bench.GOLDEN_FRAMES["_t"]
+
+
+def test_full_and_dump_outputs_are_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_the_film_and_its_counts(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the film of the last timed step as film.npy (float32, H x W x 5) and [samples, segments] as counts.npy;
+    a film over the size cap becomes the same seeded sample of its pixels on every run"""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    film = np.random.default_rng(3).random((6, 8, 5)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), film, 48 * 4, 1234)
+    assert sorted(os.listdir(tmp_path / "a")) == ["counts.npy", "film.npy"]
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    counts = np.load(tmp_path / "a" / "counts.npy")
+    assert counts.dtype == np.float64 and counts.tolist() == [192.0, 1234.0]
+    monkeypatch.setattr(bench, "DUMP_FILM_MAX_BYTES", 10 * 5 * 4)                 # room for ten pixels
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), film, 1, 2)
+        assert sorted(os.listdir(tmp_path / d)) == ["counts.npy", "film_sample.npy", "film_sample_index.npy"]
+    idx = np.load(tmp_path / "b" / "film_sample_index.npy")
+    smp = np.load(tmp_path / "b" / "film_sample.npy")
+    assert idx.dtype == np.float64 and len(idx) == 10 and np.all(np.diff(idx) > 0)
+    assert smp.dtype == np.float32 and np.array_equal(smp, film.reshape(-1, 5)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "film_sample_index.npy"))

@@ -613,24 +613,28 @@ def test_roughdielectric_against_float64_restatement(native, oracle, kw):
     assert n_r > 30 and n_t > 200 and n_ev > 300
 
 
+# sha256 of the 95 x 3 CIE 1931 values followed by the 95 D65 values, as little-endian float64: the digest of the reference's
+# tables (src/libcore/spectrum.cpp:110-186, src/spectra/d65.cpp:12-25), which csrc/miw/cie_data.h was checked to hold value for value
+CIE_D65_SHA256 = "34cf5367aab345b19c5d40931a6bef2ba193f31f21916d101009c3ae350632e3"
+
+
 def _reference_tables():
-    """CIE 1931 (src/libcore/spectrum.cpp:110-186, 95 samples x 3, 360 - 830 nm) and D65 (src/spectra/d65.cpp:12-25), parsed from
-    the reference's sources where they lie — this test runs only where /root/reference exists (the CPU tier's box)."""
+    """CIE 1931 (95 samples x 3, 360 - 830 nm) and D65 (95 samples), parsed from the text of csrc/miw/cie_data.h (not compiled in) and
+    pinned to the reference's own values by CIE_D65_SHA256: a table edited or regenerated wrongly fails here, before any sum below."""
+    import hashlib
     import os
     import re
-    ref = "/root/reference"
-    if not os.path.exists(ref + "/src/libcore/spectrum.cpp"):
-        pytest.skip("the reference tree is not on this box")
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mitsuba2_amd", "csrc", "miw", "cie_data.h")).read()
     num = r"[-+]?\d*\.?\d+(?:[eE][-+]?\d+)?"
-    txt = open(ref + "/src/libcore/spectrum.cpp").read()
-    body = txt[txt.index("cie1931_tbl[MTS_CIE_SAMPLES * 3] = {"):]
-    body = body[body.index("{") + 1:body.index("};")]
-    cie = np.array([float(x) for x in re.findall(num, re.sub(r"(?<=\d)f", "", body))]).reshape(3, 95)
-    txt = open(ref + "/src/spectra/d65.cpp").read()
-    body = txt[txt.index("const float data[95] = {"):]
-    body = body[body.index("{") + 1:body.index("};")]
-    d65 = np.array([float(x) for x in re.findall(num, re.sub(r"(?<=\d)f", "", body))])
+
+    def table(name):
+        head = "#define %s \\" % name
+        body = txt[txt.index(head) + len(head):]
+        body = body[:body.index("\n\n")] if "\n\n" in body else body
+        return np.array([float(x) for x in re.findall(num, re.sub(r"(?<=\d)f", "", body.replace("(float)", "")))])
+    cie, d65 = table("MIW_CIE1931_TABLE").reshape(3, 95), table("MIW_D65_TABLE")
     assert cie.shape == (3, 95) and d65.shape == (95,)
+    assert hashlib.sha256(np.concatenate([cie.ravel(), d65]).astype("<f8").tobytes()).hexdigest() == CIE_D65_SHA256
     return cie, d65
 
 
@@ -638,7 +642,7 @@ def test_spectral_leaves_against_float64_restatement(native, oracle_spectral):
     """scalar_spectral (config 5): sample_shifted (math.h:419-442) + sample_rgb_spectrum (spectrum.h:271-285), srgb_model_eval
     (srgb.h:9-23), the srgb_d65 emitter spectrum = the upsampled colour times the D65 table (srgb_d65.cpp:56-62, d65.cpp:50-66,
     `regular`'s linear interpolation distr_1d.h:378-392) and spectrum_to_xyz over the CIE 1931 table (spectrum.h:147-217) —
-    with both tables read from the reference's sources, not from the product's generated header."""
+    with both tables pinned to the reference's values by digest (_reference_tables)."""
     cie, d65 = _reference_tables()
 
     def lerp_table(tab, lam):

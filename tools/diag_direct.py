@@ -1,5 +1,5 @@
-import sys, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mitsuba2_amd import api, scenes
 scene, sensor = scenes.cornell_box(96, 64, 8, diffuse_only=False, device=-1, ball_level=2)
 dev = api.Device(0); dev.upload(scene.desc())

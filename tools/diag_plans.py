@@ -4,8 +4,8 @@ Moeller-Trumbore hits described in DESIGN.md section 2 (one sample in 1.3e8).
 
     python tools/diag_plans.py 1920 1080 64
 """
-import sys, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mitsuba2_amd import api as native, scenes
 W, H, SPP = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 scene, sensor = scenes.cornell_box(W, H, SPP, device=-1)

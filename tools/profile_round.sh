@@ -34,7 +34,7 @@ line() {  # line <name> [ENV=VAL ...] -- <bench args...>: one bench line into $o
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
   env "${envs[@]}" timeout 400 python bench.py --no-cpu-baseline --no-extras "$@" > $out/${tag}_${name}.log 2> $out/${tag}_${name}.err
 }
-env -u MIW_BENCH_NO_LIVE timeout 900 python bench.py > $out/${tag}_bench_c2.log 2> $out/${tag}_bench_c2.err      # THE default line: live counters, CPU leg, extras at the configured spp
+env -u MIW_BENCH_NO_LIVE timeout 900 python bench.py --full > $out/${tag}_bench_c2.log 2> $out/${tag}_bench_c2.err      # THE default line, in full: live counters, CPU leg, parity, extras at the configured spp
 C3="--scene matball --steps 1 --warmup 1"; C4="--scene interior --steps 1 --warmup 1"
 line bench_c3 -- $C3 --spp 1024                                   # configs[2] as configured
 line bench_c3_bvh4 MIW_BVH8=0 -- $C3 --spp 256                    # the 4-wide walk (round 4's tree) on the same build
