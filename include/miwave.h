@@ -417,6 +417,31 @@ mi_status mi_pdf_emitter_direction(mi_ctx *ctx, int32_t emitter, const float *re
  * envmap.cpp:134-147); zero where si[i].emitter_index < 0. spec: N n floats. */
 mi_status mi_emitter_eval(mi_ctx *ctx, const mi_surface_interaction *si, const float *wavelengths, float *spec, uint64_t n);
 
+/* SamplingIntegrator::sample(scene, sampler, ray) -> (Spectrum, Mask) (include/mitsuba/render/integrator.h:114-119) for n
+ * caller-supplied rays: PathIntegrator::sample (path.cpp:100-211) or DirectIntegrator::sample (direct.cpp:105-198). The moment
+ * integrator is NOT served (its sample() returns AOVs); neither are ray differentials and media. */
+typedef struct {
+    uint32_t struct_size;            /* sizeof(mi_sample_cfg) of the caller: the library refuses a size it does not know */
+    int32_t  integrator;             /* MI_INTEGRATOR_PATH | MI_INTEGRATOR_DIRECT                                        */
+    int32_t  max_depth, rr_depth;    /* path                                                                             */
+    uint32_t emitter_samples, bsdf_samples;  int32_t hide_emitters;   /* direct                                         */
+    int32_t  on_device;              /* 0: every pointer below is a host pointer; 1: device pointers (no copies)          */
+} mi_sample_cfg;                     /* 8 words */
+/*   rays        SoA, as for mi_trace (o, d, mint, maxt)
+ *   wavelengths 4 n floats (scalar_spectral library; ray.wavelengths), else NULL
+ *   rng_state   n u64, IN/OUT: the PCG32 state of each ray's sampler on entry; on return the state after the draws the
+ *               integrator made, so that a caller can chain samples exactly as render_sample does
+ *   rng_inc     n u64, or NULL = the default stream's increment (what Sampler::seed produces in scalar mode)
+ *   spec        N n floats (N = mi_spectrum_channels(); ray i at spec[N i ..]): the returned Spectrum — NOT multiplied by the
+ *               ray weight, NOT converted to XYZ
+ *   valid       n bytes: the returned Mask (path.cpp:121 valid_ray / direct.cpp:114)
+ * A ray's result depends on its own inputs only (not on n, the order of the rays or on_device). on_device = 0 stages the rays
+ * through context-owned buffers in chunks, so n is bounded by host memory only; on_device = 1 reads and writes the caller's
+ * device arrays in place. Runs on the context's stream and returns when the results are there; mi_cancel() from another thread
+ * ends it between chunks with MI_ERR_CANCELLED. n == 0: MI_OK. */
+mi_status mi_sample(mi_ctx *ctx, const mi_sample_cfg *cfg, const mi_rays_soa *rays, const float *wavelengths,
+                    uint64_t *rng_state, const uint64_t *rng_inc, float *spec, uint8_t *valid, uint64_t n);
+
 /* SamplingIntegrator::render (integrator.cpp:51-179) with PathIntegrator::sample
  * (src/integrators/path.cpp:100-211): renders the ctx's tile shard into `film`.
  * Returns MI_ERR_CANCELLED if mi_cancel()/timeout stopped it (film holds the

@@ -132,6 +132,11 @@ class mi_counters(C.Structure):
                 ("job_chunk", C.c_uint32), ("job_chunks", C.c_uint32)]
 
 
+class mi_sample_cfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("integrator", C.c_int32), ("max_depth", C.c_int32), ("rr_depth", C.c_int32),
+                ("emitter_samples", C.c_uint32), ("bsdf_samples", C.c_uint32), ("hide_emitters", C.c_int32), ("on_device", C.c_int32)]
+
+
 MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
 MI_BVH_FORCE_TREE, MI_BVH_NO_LEAF_FILTER, MI_BVH_RADIX_TREE = 0x10, 0x20, 0x40      # flags of mi_bvh_build's quality argument
 MI_OK, MI_ERR_INVALID, MI_ERR_DEVICE, MI_ERR_STATE, MI_ERR_CANCELLED = 0, -1, -2, -3, -4
@@ -142,7 +147,7 @@ MI_EVAL_STRIDES = {0: (2, 8), 1: (1, 2), 2: (2, 4), 3: (10, 13), 4: (2, 4), 5: (
 # every symbol include/miwave.h declares (tests check that the library exports all of them)
 MI_SYMBOLS = ["mi_spectrum_channels", "mi_device_count", "mi_create", "mi_destroy", "mi_set_stream", "mi_scene_upload", "mi_bvh_build",
               "mi_trace", "mi_render", "mi_cancel", "mi_get_counters", "mi_last_error", "mi_eval", "mi_selftest",
-              "mi_ray_intersect", "mi_sample_emitter_direction", "mi_pdf_emitter_direction", "mi_emitter_eval",
+              "mi_ray_intersect", "mi_sample_emitter_direction", "mi_pdf_emitter_direction", "mi_emitter_eval", "mi_sample",
               "mi_film_alloc", "mi_film_free", "mi_film_download", "mi_film_reduce",
               "mi_set_option", "mi_get_option", "mi_option_count", "mi_option_name", "mi_option_help"]
 
@@ -201,6 +206,8 @@ def load_device_lib(variant="scalar_rgb"):
     lib.mi_sample_emitter_direction.restype = C.c_int32
     lib.mi_pdf_emitter_direction.argtypes = [vp, C.c_int32, c_float_p, dsp, c_float_p, C.c_uint64]; lib.mi_pdf_emitter_direction.restype = C.c_int32
     lib.mi_emitter_eval.argtypes = [vp, sip, c_float_p, c_float_p, C.c_uint64]; lib.mi_emitter_eval.restype = C.c_int32
+    # (the arrays are addresses: host or, with mi_sample_cfg::on_device, device memory)
+    lib.mi_sample.argtypes = [vp, C.POINTER(mi_sample_cfg), C.POINTER(mi_rays_soa), vp, vp, vp, vp, vp, C.c_uint64]; lib.mi_sample.restype = C.c_int32
     return lib
 
 
@@ -253,6 +260,10 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_film_data": (c_float_p, [vp, C.POINTER(u64)]), "mih_film_develop_rgb": (i32, [vp, c_float_p]),
         "mih_sampler_create": (vp, [vp]), "mih_sampler_destroy": (None, [vp]),
         "mih_sampler_seed": (None, [vp, u64]), "mih_sampler_next_1d": (f, [vp]),
+        "mih_sampler_get_state": (None, [vp, C.POINTER(u64), C.POINTER(u64)]), "mih_sampler_set_state": (None, [vp, u64, u64]),
+        "mih_integrator_sample": (i32, [vp, vp, vp, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_int)]),
+        "mih_integrator_sample_batch": (i32, [vp, vp, C.POINTER(mi_rays_soa), vp, vp, vp, vp, vp, u64, i32]),
+        "mih_integrator_sample_cfg": (i32, [vp, C.POINTER(mi_sample_cfg)]),
         "mih_sensor_create": (vp, [vp, vp, vp]), "mih_sensor_destroy": (None, [vp]),
         "mih_sensor_sample_ray": (i32, [vp, f, f, c_float_p]), "mih_sensor_x_fov": (f, [vp]),
         "mih_integrator_create": (vp, [vp]), "mih_integrator_destroy": (None, [vp]),

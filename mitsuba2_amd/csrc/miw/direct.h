@@ -193,4 +193,63 @@ MIW_HD void pixel_stream_render_direct(const RenderParams &P, const SceneView &s
     }
 }
 
+// DirectIntegrator::sample for the ray in L.ray, direct.cpp:113-195: the query of that ray, then the queries of the rays that leave
+// the surface point. Adds into L.res, sets LF_VALID_RAY, draws from L.rng. This is the body of pixel_stream_render_direct's loop,
+// statement for statement (the functions it calls are shared); that loop keeps its own inline copy because moving it into a
+// function changed the register allocation of the direct render kernels, which must stay what they were measured as.
+template <int Mats, bool Analytic, typename Trace2, typename Cnt>
+MIW_HD void direct_sample_ray(const RenderParams &P, const SceneView &sc, LaneRegs &L, Trace2 &trace2, Cnt *cnt_local) {
+    const uint32_t n_emitter = P.direct.emitter_samples, n_bsdf = P.direct.bsdf_samples;
+    const V3 o0 = L.ray.o, d0 = L.ray.d;
+    F4 h0; bool unused = false;
+    trace2(o0, L.ray.mint, d0, L.ray.maxt, true, v3(0.f), -1.f, false, h0, unused);
+    {
+        SurfaceInteraction si; BsdfSide bsdf;
+        bsdf.b = sc.bsdfs; bsdf.flip = bsdf.none = false; bsdf.flags = 0;
+        if (direct_primary<Mats, Analytic>(P, sc, L, h0, o0, si, bsdf, cnt_local)) {
+            uint32_t ie = (bsdf.flags & BSDF_Smooth) ? 0u : n_emitter, ib = 0;   // :134-136: no emitter samples (and no draws) otherwise
+            for (;;) {
+                ShadowOut sh; sh.has = false; sh.d = v3(0.f); sh.maxt = -1.f; sh.c = spec(0.f);
+                DirectPending pend; pend.bsdf_val = spec(0.f); pend.pdf = 0.f; pend.delta = false;
+                bool queued = false;
+                while (ie < n_emitter && !queued) { ++ie; queued = direct_emitter_sample<Mats, Analytic>(P, sc, L, si, bsdf, sh, cnt_local); }
+                if (ie == n_emitter)                           // the last shadow ray travels with the first BSDF-sampled ray
+                    while (ib < n_bsdf && !(L.ray.maxt >= 0.f)) { ++ib; if (direct_bsdf_sample<Mats>(sc, L, si, bsdf, pend)) queued = true; }
+                if (!queued) break;
+                const V3 o = L.ray.o;
+                const bool has_e = L.ray.maxt >= 0.f;
+                F4 h; bool occluded = false;
+                trace2(o, L.ray.mint, L.ray.d, L.ray.maxt, has_e, sh.d, sh.maxt, sh.has, h, occluded);
+                if (sh.has && !occluded) L.res = L.res + sh.c;     // direct.cpp:159 of the emitter sample that was in flight
+                if (has_e) {
+                    direct_bsdf_hit<Analytic>(P, sc, L, h, o, pend);
+                    L.ray.d = v3(0.f); L.ray.maxt = -1.f;
+                }
+                if (ie == n_emitter && ib == n_bsdf) break;
+                int32_t emitter; uint32_t bsdf_index;              // more samples from this point: the interaction again
+                hit_surface_interaction<Analytic, Mats == MATS_ALL>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
+                bsdf = bsdf_side(sc.bsdfs, bsdf_index, si.wi);
+            }
+        }
+    }
+}
+
+// The ray-fed twin (path.h: ray_stream_sample — same `feed` contract): DirectIntegrator::sample for caller-supplied rays.
+template <int Mats, bool Analytic, typename Feed, typename Trace2, typename Cnt>
+MIW_HD void ray_stream_sample_direct(const RenderParams &P, const SceneView &sc, Feed &feed, Trace2 trace2, Cnt *cnt_local) {
+    LaneRegs L;
+    L.flags = LF_DONE; L.rng.state = 0; L.rng.inc = MIW_PCG32_SCALAR_INC;
+    for (;;) {
+        if (L.flags & LF_DONE) {
+            if (!feed.fetch(L)) break;
+            lane_begin_path(L);
+            continue;
+        }
+        direct_sample_ray<Mats, Analytic>(P, sc, L, trace2, cnt_local);
+        feed.store(L);
+        if (cnt_local) cnt_local->samples++;
+        L.flags = LF_DONE;
+    }
+}
+
 } // namespace miw

@@ -542,6 +542,49 @@ MIW_HD void pixel_stream_render(const RenderParams &P, const SceneView &sc, uint
     }
 }
 
+// The ray-fed twin of pixel_stream_render: SamplingIntegrator::sample (integrator.h:114-119) for rays the CALLER supplies.
+// Same loop, same trace2 contract, same path_step; what differs is where a job comes from and where it goes:
+//   feed.fetch(L)  hands this lane its next ray — L.ray, L.wl and L.rng (state AND increment) — or returns false: none left;
+//   feed.store(L)  takes the result of the ray fetched last: L.res, L.flags & LF_VALID_RAY, L.rng.state.
+// No camera, no film: nothing of lane_begin_sample / lane_finish_sample, P.sensor, P.film and P.spp is read. As there, a lane
+// that finishes a ray fetches the next one INSIDE the loop, so the other lanes of its wavefront never wait for it.
+MIW_HD void lane_begin_path(LaneRegs &L) {
+    L.tp = spec(1.f); L.res = spec(0.f); L.eta = 1.f; L.prev_pdf = 0.f;   // path.cpp:111-116
+    L.flags = 1u | LF_RAY_ACTIVE;                        // depth = 1
+    L.sample_idx = 0; L.pos = v2(0.f, 0.f); L.ray_weight = spec(1.f);
+}
+template <int Mats = MATS_ALL, bool Analytic = true, typename Feed, typename Trace2, typename Cnt>
+MIW_HD void ray_stream_sample(const RenderParams &P, const SceneView &sc, Feed &feed, Trace2 trace2, Cnt *cnt_local) {
+    LaneRegs L;
+    L.flags = LF_DONE; L.rng.state = 0; L.rng.inc = MIW_PCG32_SCALAR_INC;
+    bool dead_pending = false;
+    ShadowOut sh; sh.has = false; sh.d = v3(0.f); sh.maxt = -1.f; sh.c = spec(0.f);
+    for (;;) {
+        if (L.flags & LF_DONE) {
+            if (!feed.fetch(L)) break;
+            lane_begin_path(L);
+            continue;
+        }
+        const V3 o = L.ray.o;
+        F4 h; bool occluded = false;
+        trace2(o, L.ray.mint, L.ray.d, L.ray.maxt, !dead_pending, sh.d, sh.maxt, sh.has, h, occluded);
+        if (sh.has && !occluded) L.res = L.res + sh.c;              // path.cpp:171 of the previous vertex
+        sh.has = false;
+        if (!dead_pending) {
+            const int r = path_step<Mats, Analytic>(P, sc, L, h, [o]() { return o; }, sh, cnt_local);
+            if (r == STEP_DEAD_PENDING) { dead_pending = true; continue; }   // one more pass for its shadow ray
+            if (r == STEP_CONTINUE) continue;
+        }
+        dead_pending = false;
+        feed.store(L);
+        if (cnt_local) cnt_local->samples++;
+        L.flags = LF_DONE;
+    }
+}
+
+template <int Mats, bool Analytic, typename Feed, typename Trace2, typename Cnt>
+MIW_HD void ray_stream_sample_direct(const RenderParams &P, const SceneView &sc, Feed &feed, Trace2 trace2, Cnt *cnt_local);   // direct.h
+
 template <int Mats, bool Analytic, typename Work, typename Trace2, typename Cnt>
 MIW_HD void pixel_stream_render_direct(const RenderParams &P, const SceneView &sc, uint32_t sample_end, Work &work,
                                        Trace2 trace2, Cnt *cnt_local);     // direct.h

@@ -95,6 +95,7 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/stream_trace.h"
 #include "device/film_kernels.h"
 #include "device/eval_kernels.h"
+#include "device/sample_kernel.h"
 
 __global__ void k_iota(uint32_t *out, uint32_t n) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = i; }
 
@@ -240,6 +241,8 @@ struct mi_ctx {
     bool replay_enqueued = false;       // this frame's k_film_lanes launches already sit in the replay streams (assemble_film only joins)
     uint32_t replay_launches = 0;
 
+    DevBuf<unsigned char> d_sample_stage; DevBuf<uint32_t> d_next_ray;   // mi_sample: the staged chunk of a host-pointer call, the ray queue's counter
+
     std::vector<hipEvent_t> ev_pool;
     mi_counters counters{};
 };
@@ -296,7 +299,7 @@ void mi_destroy(mi_ctx *c) {
     c->d_accum.release(); c->d_out.release(); c->d_next_pixel.release(); c->d_lane_cost.release(); c->d_cost_sorted.release(); c->d_lane_iota.release(); c->d_lane_sorted.release(); c->d_place_tmp.release(); c->d_piece_list.release(); c->d_simd_ids.release(); c->d_lists.release(); c->d_list_counts.release(); c->d_block_ids.release(); c->d_tile_list.release(); c->d_cnt.release();
     c->q_log_pos.release(); c->q_log_val.release(); c->q_log_rec.release(); c->d_fc_thr.release(); c->d_fc_w.release(); c->d_block_tile.release(); c->d_tiles.release();
     for (hipEvent_t e : c->ev_pool) (void) hipEventDestroy(e);
-    c->d_group_done.release(); c->d_group_expected.release();
+    c->d_group_done.release(); c->d_group_expected.release(); c->d_sample_stage.release(); c->d_next_ray.release();
     if (c->h_group_flag) (void) hipHostFree(c->h_group_flag);
     if (c->ev_fork) (void) hipEventDestroy(c->ev_fork);
     for (int i = 0; i < 3; ++i) { if (c->ev_join[i]) (void) hipEventDestroy(c->ev_join[i]); if (c->stream2[i]) (void) hipStreamDestroy(c->stream2[i]); }
@@ -1149,6 +1152,11 @@ mi_status mi_emitter_eval(mi_ctx *c, const mi_surface_interaction *si, const flo
 }
 
 // ---- render ----------------------------------------------------------------------------
+static void direct_constants(DirectRec &D, uint32_t ne, uint32_t nb, bool hide_emitters) {   // direct.cpp:82-103
+    D.emitter_samples = ne; D.bsdf_samples = nb; D.hide_emitters = hide_emitters ? 1u : 0u;
+    D.weight_bsdf = 1.f / (float) nb; D.weight_lum = 1.f / (float) ne;
+    D.frac_bsdf = (float) nb / (float) (ne + nb); D.frac_lum = (float) ne / (float) (ne + nb);
+}
 static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &P) {
     if (cfg->crop_w <= 0 || cfg->crop_h <= 0 || cfg->crop_x < 0 || cfg->crop_y < 0)
         return fail(c, MI_ERR_INVALID, "render: bad crop window");
@@ -1175,9 +1183,7 @@ static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &
         const uint32_t ne = cfg->emitter_samples, nb = cfg->bsdf_samples;
         if (ne + nb == 0) return fail(c, MI_ERR_INVALID, "Must have at least 1 BSDF or emitter sample!");
         P.integrator = INTEG_DIRECT;
-        P.direct.emitter_samples = ne; P.direct.bsdf_samples = nb; P.direct.hide_emitters = cfg->hide_emitters ? 1u : 0u;
-        P.direct.weight_bsdf = 1.f / (float) nb; P.direct.weight_lum = 1.f / (float) ne;
-        P.direct.frac_bsdf = (float) nb / (float) (ne + nb); P.direct.frac_lum = (float) ne / (float) (ne + nb);
+        direct_constants(P.direct, ne, nb, cfg->hide_emitters != 0);
     } else if (cfg->integrator != MI_INTEGRATOR_PATH)
         return fail(c, MI_ERR_INVALID, "render: unknown integrator %d", cfg->integrator);
     if (cfg->moment_pass < MI_MOMENT_OFF || cfg->moment_pass > MI_MOMENT_SQUARES) return fail(c, MI_ERR_INVALID, "render: moment_pass must be 0, 1 or 2");
@@ -1186,6 +1192,134 @@ static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &
 #endif
     P.moment_pass = (uint32_t) cfg->moment_pass;
     render_params_prepare(P);
+    return MI_OK;
+}
+
+// ---- mi_sample: SamplingIntegrator::sample for caller-supplied rays (device/sample_kernel.h) ------------------------------
+// Rays per launch. Host-pointer calls stage one chunk at a time in a buffer the context keeps (88 + 4 N bytes per ray: 200 MB),
+// so n is bounded by the caller's memory only; device-pointer calls are cut as well, so that mi_cancel is looked at in between
+// (and the queue's 32-bit counter never wraps).
+#define MIW_SAMPLE_CHUNK_HOST (1u << 21)
+#define MIW_SAMPLE_CHUNK_DEVICE (1u << 26)
+static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO &io, hipStream_t s) {
+    const bool tiny = c->lds_cfg.brute != 0, direct = P.integrator == INTEG_DIRECT, small = c->view.tri_count <= 32u;
+    const bool trio_on = !(c->opt.get("MIW_TRIO") && atoi(c->opt.get("MIW_TRIO")) == 0);
+    const bool trio_kernel = c->trio && trio_on && c->rects.empty() && !c->textured;
+    // persistent grid: as many workgroups per CU as the kernel is compiled for wavefronts per SIMD (sample_kernel.h), never more than the rays need
+    const unsigned waves = direct ? (unsigned) MIW_DIRECT_WAVES : tiny ? 4u : (unsigned) MIW_TREE_WAVES;
+    const dim3 grid(std::min<unsigned>((io.n + MIW_BLOCK - 1u) / MIW_BLOCK, (unsigned) c->cu_count * waves)), block(MIW_BLOCK);
+    HIP_TRY(c, hipMemsetAsync(c->d_next_ray.p, 0, sizeof(uint32_t), s));
+#define MIW_SAMPLE_LAUNCH(T, M, A, I) hipLaunchKernelGGL((k_sample_rays<T, M, A, I>), grid, block, c->lds_bytes, s, P, c->view, io, c->lds_cfg, c->d_next_ray.p)
+    // the instantiation mi_render would pick for this scene: no BSDF dispatch when every shape is plain diffuse, no texture lookups
+    // without texture coordinates, no analytic shapes where there are none
+    if (direct) {
+        if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_DIRECT);
+        else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_DIRECT);
+        else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_DIRECT);
+        else MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, true, INTEG_DIRECT);
+    }
+    else if (tiny && c->diffuse_only && small) MIW_SAMPLE_LAUNCH(2, MATS_DIFFUSE, false, INTEG_PATH);
+    else if (tiny && c->diffuse_only) MIW_SAMPLE_LAUNCH(1, MATS_DIFFUSE, false, INTEG_PATH);
+    else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_PATH);
+    else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_PATH);
+    else if (tiny && small) MIW_SAMPLE_LAUNCH(2, MATS_PLAIN, false, INTEG_PATH);
+    else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_PATH);
+    else if (trio_kernel) MIW_SAMPLE_LAUNCH(0, MATS_TRIO, false, INTEG_PATH);
+    else if (c->rects.empty()) MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, false, INTEG_PATH);
+    else MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, true, INTEG_PATH);
+#undef MIW_SAMPLE_LAUNCH
+    HIP_TRY(c, hipGetLastError());
+    return MI_OK;
+}
+
+static std::string sample_cfg_problem(const mi_sample_cfg *cfg) {
+    char buf[160];
+    if (cfg->struct_size != sizeof(mi_sample_cfg)) {
+        snprintf(buf, sizeof buf, "mi_sample: unknown mi_sample_cfg::struct_size %u (this library: %zu)", cfg->struct_size, sizeof(mi_sample_cfg));
+        return buf;
+    }
+    if (cfg->integrator == MI_INTEGRATOR_PATH) {
+        if (cfg->rr_depth <= 0) return "\"rr_depth\" must be set to a value greater than zero!";
+        if (cfg->max_depth < -1) return "\"max_depth\" must be set to -1 (infinite) or a value >= 0";
+    } else if (cfg->integrator == MI_INTEGRATOR_DIRECT) {
+        if (cfg->emitter_samples + cfg->bsdf_samples == 0) return "Must have at least 1 BSDF or emitter sample!";
+    } else {
+        snprintf(buf, sizeof buf, "mi_sample: unknown integrator %d (served: MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT)", cfg->integrator);
+        return buf;
+    }
+    return std::string();
+}
+
+mi_status mi_sample(mi_ctx *c, const mi_sample_cfg *cfg, const mi_rays_soa *rays, const float *wavelengths,
+                    uint64_t *rng_state, const uint64_t *rng_inc, float *spec_out, uint8_t *valid, uint64_t n) {
+    if (!cfg) return MI_ERR_INVALID;
+    {   // the job description first: a caller compiled against another header must hear so whatever else is wrong (no context needed)
+        const std::string why = sample_cfg_problem(cfg);
+        if (!why.empty()) { if (c) c->error = why; else g_global_error = why; return MI_ERR_INVALID; }
+    }
+    if (!c) return MI_ERR_INVALID;
+    if (!rays || !rng_state || !spec_out || !valid) return fail(c, MI_ERR_INVALID, "mi_sample: null rays / rng_state / spec / valid");
+    if (!c->have_bvh) return fail(c, MI_ERR_STATE, "mi_sample: call mi_scene_upload and mi_bvh_build first");
+    RenderParams P;
+    memset(&P, 0, sizeof P);
+    P.spp = 1u; P.max_depth = cfg->max_depth; P.rr_depth = cfg->rr_depth;
+    if (cfg->integrator == MI_INTEGRATOR_DIRECT) {
+        P.integrator = INTEG_DIRECT;
+        direct_constants(P.direct, cfg->emitter_samples, cfg->bsdf_samples, cfg->hide_emitters != 0);
+    }
+    if (MIW_SPECTRAL && !wavelengths) return fail(c, MI_ERR_INVALID, "mi_sample: the scalar_spectral library needs wavelengths");
+    const float *src[8] = { rays->ox, rays->oy, rays->oz, rays->dx, rays->dy, rays->dz, rays->mint, rays->maxt };
+    for (int k = 0; k < 8; ++k) if (!src[k]) return fail(c, MI_ERR_INVALID, "mi_sample: null ray array");
+    if (n == 0) return MI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    c->cancel.store(0);
+    HIP_TRY(c, c->d_next_ray.resize(1));
+    const bool dev = cfg->on_device != 0;
+    const uint64_t chunk = dev ? MIW_SAMPLE_CHUNK_DEVICE : MIW_SAMPLE_CHUNK_HOST;
+    // staged chunk of a host-pointer call: [8 ray arrays][wavelengths][rng state][rng inc][spec][valid], every array 16-byte aligned
+    const uint64_t m_max = std::min<uint64_t>(n, chunk), m_pad = (m_max + 15u) & ~(uint64_t) 15u;
+    const size_t off_wl = 8 * m_pad * 4, off_st = off_wl + (MIW_SPECTRAL ? 4 * m_pad * 4 : 0), off_inc = off_st + m_pad * 8,
+                 off_spec = off_inc + m_pad * 8, off_valid = off_spec + MIW_SPEC_N * m_pad * 4, stage_bytes = off_valid + m_pad;
+    if (!dev) HIP_TRY(c, c->d_sample_stage.resize(stage_bytes));
+    for (uint64_t done = 0; done < n; done += chunk) {
+        if (c->cancel.load()) return fail(c, MI_ERR_CANCELLED, "mi_sample: cancelled after %llu of %llu rays", (unsigned long long) done, (unsigned long long) n);
+        const uint64_t m = std::min<uint64_t>(chunk, n - done);
+        SampleIO io;
+        io.n = (uint32_t) m;
+        if (dev) {
+            io.R = { src[0] + done, src[1] + done, src[2] + done, src[3] + done, src[4] + done, src[5] + done, src[6] + done, src[7] + done };
+            io.wavelengths = wavelengths ? wavelengths + 4 * done : nullptr;
+            io.rng_state = rng_state + done; io.rng_inc = rng_inc ? rng_inc + done : nullptr;
+            io.spec = spec_out + MIW_SPEC_N * done; io.valid = valid + done;
+        } else {
+            unsigned char *b = c->d_sample_stage.p;
+            float *f = reinterpret_cast<float *>(b);
+            for (int k = 0; k < 8; ++k) HIP_TRY(c, hipMemcpyAsync(f + k * m_pad, src[k] + done, m * sizeof(float), hipMemcpyHostToDevice, s));
+            io.R = { f, f + m_pad, f + 2 * m_pad, f + 3 * m_pad, f + 4 * m_pad, f + 5 * m_pad, f + 6 * m_pad, f + 7 * m_pad };
+            io.wavelengths = nullptr;
+            if (MIW_SPECTRAL) {
+                HIP_TRY(c, hipMemcpyAsync(b + off_wl, wavelengths + 4 * done, 4 * m * sizeof(float), hipMemcpyHostToDevice, s));
+                io.wavelengths = reinterpret_cast<const float *>(b + off_wl);
+            }
+            HIP_TRY(c, hipMemcpyAsync(b + off_st, rng_state + done, m * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            io.rng_state = reinterpret_cast<uint64_t *>(b + off_st);
+            io.rng_inc = nullptr;
+            if (rng_inc) {
+                HIP_TRY(c, hipMemcpyAsync(b + off_inc, rng_inc + done, m * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+                io.rng_inc = reinterpret_cast<const uint64_t *>(b + off_inc);
+            }
+            io.spec = reinterpret_cast<float *>(b + off_spec); io.valid = b + off_valid;
+        }
+        const mi_status ls = sample_launch(c, P, io, s);
+        if (ls != MI_OK) return ls;
+        if (!dev) {
+            HIP_TRY(c, hipMemcpyAsync(rng_state + done, io.rng_state, m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(spec_out + MIW_SPEC_N * done, io.spec, MIW_SPEC_N * m * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(valid + done, io.valid, m, hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
     return MI_OK;
 }
 

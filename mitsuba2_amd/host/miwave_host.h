@@ -239,6 +239,10 @@ public:
     std::array<float, 2> next_2d();
     size_t sample_count() const { return m_sample_count; }
     uint64_t base_seed() const { return m_base_seed; }
+    // the PCG32 stream behind next_1d(): what SamplingIntegrator::sample takes to the device and brings back
+    uint64_t state() const { return m_state; }
+    uint64_t inc() const { return m_inc; }
+    void set_state(uint64_t state, uint64_t inc) { m_state = state; m_inc = inc | 1u; }
 private:
     size_t m_sample_count; uint64_t m_base_seed; uint64_t m_state, m_inc;
 };
@@ -555,6 +559,14 @@ public:
     bool hide_emitters() const { return m_hide_emitters; }
     // mi_render_cfg::integrator and the plugin's own parameters
     virtual void fill_integrator(mi_render_cfg &cfg) const = 0;
+    // SamplingIntegrator::sample (include/mitsuba/render/integrator.h:114-119) on the device (mi_sample): the radiance along one ray and
+    // whether it hit a surface. Draws from `sampler` exactly what the reference's sample() draws and leaves it advanced by that.
+    // wavelengths: 4 floats (scalar_spectral build; ray.wavelengths), else nullptr. A multi-GPU scene is served by its context 0.
+    virtual std::pair<Spectrum, bool> sample(const Scene *scene, IndependentSampler *sampler, const Ray3f &ray, const float *wavelengths = nullptr) const;
+    // ... for n rays at once, arrays as mi_sample takes them (include/miwave.h); on_device: they are device arrays
+    virtual void sample(const Scene *scene, const mi_rays_soa &rays, const float *wavelengths, uint64_t *rng_state, const uint64_t *rng_inc,
+                        float *spec, uint8_t *valid, uint64_t n, bool on_device = false) const;
+    void fill_sample_cfg(mi_sample_cfg &cfg) const;            // from fill_integrator
     // all passes of one job into `film5` (crop_w * crop_h * 5 floats); moment_pass = mi_render_cfg::moment_pass
     bool render_passes(Scene *scene, PerspectiveCamera *sensor, float *film5, int moment_pass);
 protected:
@@ -607,6 +619,9 @@ public:
     std::vector<std::string> aov_names() const override;
     const std::shared_ptr<SamplingIntegrator> &nested() const { return m_nested; }
     void fill_integrator(mi_render_cfg &cfg) const override { m_nested->fill_integrator(cfg); }
+    // moment.cpp:55-95: sample() returns the nested integrator's value AND its AOVs, which mi_sample does not carry: refused
+    std::pair<Spectrum, bool> sample(const Scene *, IndependentSampler *, const Ray3f &, const float * = nullptr) const override;
+    void sample(const Scene *, const mi_rays_soa &, const float *, uint64_t *, const uint64_t *, float *, uint8_t *, uint64_t, bool = false) const override;
 private:
     std::shared_ptr<SamplingIntegrator> m_nested; std::string m_name;
 };

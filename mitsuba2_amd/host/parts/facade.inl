@@ -293,6 +293,8 @@ void *mih_sampler_create(void *props) { MIH_TRY return new Box<IndependentSample
 void mih_sampler_destroy(void *s) { delete (Box<IndependentSampler> *) s; }
 void mih_sampler_seed(void *s, uint64_t off) { ((Box<IndependentSampler> *) s)->p->seed(off); }
 float mih_sampler_next_1d(void *s) { return ((Box<IndependentSampler> *) s)->p->next_1d(); }
+void mih_sampler_get_state(void *s, uint64_t *state, uint64_t *inc) { *state = ((Box<IndependentSampler> *) s)->p->state(); *inc = ((Box<IndependentSampler> *) s)->p->inc(); }
+void mih_sampler_set_state(void *s, uint64_t state, uint64_t inc) { ((Box<IndependentSampler> *) s)->p->set_state(state, inc); }
 
 void *mih_sensor_create(void *props, void *film, void *sampler) {
     MIH_TRY
@@ -342,6 +344,22 @@ int mih_render_multi(void *i, void *scene, void *sensor, int *how) {
         if (how) *how = it->last_reduce();
         return done ? 1 : 0; MIH_CATCH(-1)
 }
+// SamplingIntegrator::sample: one ray (ray8 = o.xyz d.xyz mint maxt; advances the sampler; spec_out: N floats, *valid) ...
+int mih_integrator_sample(void *i, void *scene, void *sampler, const float *ray8, const float *wavelengths, float *spec_out, int *valid) {
+    MIH_TRY
+        Ray3f r; r.o = { ray8[0], ray8[1], ray8[2] }; r.d = { ray8[3], ray8[4], ray8[5] }; r.mint = ray8[6]; r.maxt = ray8[7];
+        auto res = ((Box<SamplingIntegrator> *) i)->p->sample(scene ? ((Box<Scene> *) scene)->p.get() : nullptr, sampler ? ((Box<IndependentSampler> *) sampler)->p.get() : nullptr, r, wavelengths);
+        for (size_t k = 0; k < res.first.size(); ++k) spec_out[k] = res.first[k];
+        *valid = res.second ? 1 : 0; return 0; MIH_CATCH(-1)
+}
+// ... and n rays (arrays as mi_sample takes them, include/miwave.h)
+int mih_integrator_sample_batch(void *i, void *scene, const mi_rays_soa *rays, const float *wavelengths, uint64_t *rng_state, const uint64_t *rng_inc,
+                                float *spec_out, uint8_t *valid, uint64_t n, int on_device) {
+    MIH_TRY
+        ((Box<SamplingIntegrator> *) i)->p->sample(scene ? ((Box<Scene> *) scene)->p.get() : nullptr, *rays, wavelengths, rng_state, rng_inc, spec_out, valid, n, on_device != 0);
+        return 0; MIH_CATCH(-1)
+}
+int mih_integrator_sample_cfg(void *i, mi_sample_cfg *cfg) { MIH_TRY ((Box<SamplingIntegrator> *) i)->p->fill_sample_cfg(*cfg); return 0; MIH_CATCH(-1) }
 int mih_integrator_last_reduce(void *i) { return ((Box<SamplingIntegrator> *) i)->p->last_reduce(); }
 int mih_integrator_counters(void *i, mi_counters *out) { *out = ((Box<SamplingIntegrator> *) i)->p->counters(); return 0; }
 // Host-side job description (no GPU needed). block_ids / tiles must hold `capacity` entries.

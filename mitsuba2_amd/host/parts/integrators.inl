@@ -225,6 +225,34 @@ bool SamplingIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
     return render_passes(scene, sensor, film->storage().data(), MI_MOMENT_OFF);
 }
 
+// SamplingIntegrator::sample (integrator.h:114-119) through mi_sample
+void SamplingIntegrator::fill_sample_cfg(mi_sample_cfg &cfg) const {
+    mi_render_cfg r; std::memset(&r, 0, sizeof r);
+    fill_integrator(r);
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.struct_size = (uint32_t) sizeof cfg; cfg.integrator = r.integrator; cfg.max_depth = r.max_depth; cfg.rr_depth = r.rr_depth;
+    cfg.emitter_samples = r.emitter_samples; cfg.bsdf_samples = r.bsdf_samples; cfg.hide_emitters = r.hide_emitters;
+}
+void SamplingIntegrator::sample(const Scene *scene, const mi_rays_soa &rays, const float *wavelengths, uint64_t *rng_state, const uint64_t *rng_inc,
+                                float *spec, uint8_t *valid, uint64_t n, bool on_device) const {
+    if (!scene) Throw("sample(): null scene");
+    if (!scene->ctx()) Throw("sample(): the scene is not built on a device (Scene::build(device >= 0) first)");
+    mi_sample_cfg cfg; fill_sample_cfg(cfg);
+    cfg.on_device = on_device ? 1 : 0;
+    if (mi_sample(scene->ctx(), &cfg, &rays, wavelengths, rng_state, rng_inc, spec, valid, n) != MI_OK)
+        Throw(std::string("mi_sample: ") + mi_last_error(scene->ctx()));
+}
+std::pair<Spectrum, bool> SamplingIntegrator::sample(const Scene *scene, IndependentSampler *sampler, const Ray3f &ray, const float *wavelengths) const {
+    if (!sampler) Throw("sample(): null sampler");
+    float r[8] = { ray.o[0], ray.o[1], ray.o[2], ray.d[0], ray.d[1], ray.d[2], ray.mint, ray.maxt };
+    const mi_rays_soa rays = { &r[0], &r[1], &r[2], &r[3], &r[4], &r[5], &r[6], &r[7] };
+    uint64_t state = sampler->state(); const uint64_t inc = sampler->inc();
+    Spectrum value{}; uint8_t valid = 0;
+    sample(scene, rays, wavelengths, &state, &inc, value.data(), &valid, 1, false);
+    sampler->set_state(state, inc);
+    return { value, valid != 0 };
+}
+
 // moment.cpp:33-53
 MomentIntegrator::MomentIntegrator(const Properties &props, std::shared_ptr<SamplingIntegrator> nested, std::string nested_name)
     : SamplingIntegrator(props), m_nested(std::move(nested)), m_name(std::move(nested_name)) {
@@ -261,4 +289,10 @@ bool MomentIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
         for (int k = 0; k < 3; ++k) { o[5 + k] = v[k]; o[8 + k] = q[k]; }
     }
     return ok;
+}
+std::pair<Spectrum, bool> MomentIntegrator::sample(const Scene *, IndependentSampler *, const Ray3f &, const float *) const {
+    Throw("moment: sample() returns AOVs, which the device entry point does not serve (NotImplementedError)");
+}
+void MomentIntegrator::sample(const Scene *, const mi_rays_soa &, const float *, uint64_t *, const uint64_t *, float *, uint8_t *, uint64_t, bool) const {
+    Throw("moment: sample() returns AOVs, which the device entry point does not serve (NotImplementedError)");
 }
