@@ -14,168 +14,8 @@ import math
 import numpy as np
 import pytest
 
-PI = math.pi
-
-
-# ---------------------------------------------------------------- warp.h
-def disk_concentric(u):
-    """core/warp.h:54-90"""
-    x, y = 2.0 * u[0] - 1.0, 2.0 * u[1] - 1.0
-    if x == 0 and y == 0:
-        return 0.0, 0.0
-    if abs(x) < abs(y):
-        r, phi = y, 0.5 * PI - 0.25 * PI * x / y
-    else:
-        r, phi = x, 0.25 * PI * y / x
-    return r * math.cos(phi), r * math.sin(phi)
-
-
-def cosine_hemisphere(u):
-    """core/warp.h:325-334"""
-    px, py = disk_concentric(u)
-    return np.array([px, py, math.sqrt(max(0.0, 1.0 - px * px - py * py))])
-
-
-# ---------------------------------------------------------------- fresnel.h
-def fresnel(cos_i, eta):
-    """render/fresnel.h:34-70 -> r, cos_theta_t, eta_it, eta_ti"""
-    outside = cos_i >= 0
-    eta_it, eta_ti = (eta, 1 / eta) if outside else (1 / eta, eta)
-    cos_t_sqr = 1 - (1 - cos_i * cos_i) * eta_ti * eta_ti
-    ci, ct = abs(cos_i), math.sqrt(max(0.0, cos_t_sqr))
-    if eta == 1:
-        r = 0.0
-    elif ci == 0:
-        r = 1.0
-    else:
-        a_s = (ci - eta_it * ct) / (ci + eta_it * ct)
-        a_p = (ct - eta_it * ci) / (ct + eta_it * ci)
-        r = 0.5 * (a_s * a_s + a_p * a_p)
-    return r, (-ct if cos_i >= 0 else ct), eta_it, eta_ti          # mulsign_neg(cos_theta_t_abs, cos_theta_i)
-
-
-def fresnel_conductor(cos_i, eta, k):
-    """render/fresnel.h:92-116 (per channel)"""
-    c2 = cos_i * cos_i
-    s2 = 1 - c2
-    s4 = s2 * s2
-    t1 = eta * eta - k * k - s2
-    a2pb2 = np.sqrt(np.maximum(0, t1 * t1 + 4 * k * k * eta * eta))
-    a = np.sqrt(np.maximum(0, 0.5 * (a2pb2 + t1)))
-    term1, term2 = a2pb2 + c2, 2 * cos_i * a
-    rs = (term1 - term2) / (term1 + term2)
-    term3, term4 = a2pb2 * c2 + s4, term2 * s2
-    rp = rs * (term3 - term4) / (term3 + term4)
-    return 0.5 * (rs + rp)
-
-
-# ---------------------------------------------------------------- microfacet.h
-class Microfacet:
-    def __init__(self, kind, au, av, visible):
-        self.kind, self.visible = kind, visible
-        self.au, self.av = max(au, 1e-4), max(av, 1e-4)          # configure(), microfacet.h:415-418
-
-    def eval(self, m):                                           # :184-202
-        c = m[2]
-        c2 = c * c
-        if self.kind == "beckmann":
-            res = math.exp(-((m[0] / self.au) ** 2 + (m[1] / self.av) ** 2) / c2) / (PI * self.au * self.av * c2 * c2)
-        else:
-            res = 1 / (PI * self.au * self.av * ((m[0] / self.au) ** 2 + (m[1] / self.av) ** 2 + m[2] ** 2) ** 2)
-        return res if res * c > 1e-20 else 0.0
-
-    def g1(self, v, m):                                          # :331-355
-        xy = (self.au * v[0]) ** 2 + (self.av * v[1]) ** 2
-        if xy == 0:
-            res = 1.0
-        else:
-            t2 = xy / (v[2] * v[2])
-            if self.kind == "beckmann":
-                a = 1 / math.sqrt(t2)
-                res = 1.0 if a >= 1.6 else (3.535 * a + 2.181 * a * a) / (1 + 2.276 * a + 2.577 * a * a)
-            else:
-                res = 2 / (1 + math.sqrt(1 + t2))
-        return 0.0 if np.dot(v, m) * v[2] <= 0 else res
-
-    def G(self, wi, wo, m):
-        return self.g1(wi, m) * self.g1(wo, m)
-
-    def pdf(self, wi, m):                                        # :214-223
-        if self.visible:
-            return self.eval(m) * self.g1(wi, m) * abs(np.dot(wi, m)) / wi[2]
-        return self.eval(m) * m[2]
-
-    def sample_visible_11_ggx(self, cos_i, u):                   # :395-411
-        px, py = disk_concentric(u)
-        s = 0.5 * (1 + cos_i)
-        py = (1 - s) * math.sqrt(max(0.0, 1 - px * px)) + s * py
-        z = math.sqrt(max(0.0, 1 - px * px - py * py))
-        sin_i = math.sqrt(max(0.0, 1 - cos_i * cos_i))
-        norm = 1 / (sin_i * py + cos_i * z)
-        return (cos_i * py - sin_i * z) * norm, px * norm
-
-    def sample(self, wi, u):                                     # :234-316 (GGX; Beckmann's visible branch is table-tested)
-        if not self.visible:
-            if self.au == self.av:
-                sin_phi, cos_phi = math.sin(2 * PI * u[1]), math.cos(2 * PI * u[1])
-                a2 = self.au * self.au
-            else:
-                tmp = self.av / self.au * math.tan(2 * PI * u[1])
-                cos_phi = 1 / math.sqrt(tmp * tmp + 1)
-                cos_phi = math.copysign(cos_phi, abs(u[1] - 0.5) - 0.25)
-                sin_phi = cos_phi * tmp
-                a2 = 1 / ((cos_phi / self.au) ** 2 + (sin_phi / self.av) ** 2)
-            if self.kind == "beckmann":
-                cos_t = 1 / math.sqrt(1 - a2 * math.log(1 - u[0]))
-                pdf = (1 - u[0]) / (PI * self.au * self.av * max(cos_t ** 3, 1e-20))
-            else:
-                tan2 = a2 * u[0] / (1 - u[0])
-                cos_t = 1 / math.sqrt(1 + tan2)
-                pdf = 1 / (PI * self.au * self.av * max(cos_t ** 3, 1e-20) * (1 + tan2 / a2) ** 2)
-            sin_t = math.sqrt(1 - cos_t * cos_t)
-            return np.array([cos_phi * sin_t, sin_phi * sin_t, cos_t]), pdf
-        wp = np.array([self.au * wi[0], self.av * wi[1], wi[2]])
-        wp /= np.linalg.norm(wp)
-        sin_t = math.sqrt(max(0.0, 1 - wp[2] * wp[2]))                          # Frame::sincos_phi, frame.h
-        sin_phi, cos_phi = (wp[1] / sin_t, wp[0] / sin_t) if sin_t > 1e-12 else (0.0, 1.0)
-        sx, sy = self.sample_visible_11_ggx(wp[2], u)
-        sx, sy = (cos_phi * sx - sin_phi * sy) * self.au, (sin_phi * sx + cos_phi * sy) * self.av
-        m = np.array([-sx, -sy, 1.0])
-        m /= np.linalg.norm(m)
-        return m, self.eval(m) * self.g1(wi, m) * abs(np.dot(wi, m)) / wi[2]
-
-
-# ---------------------------------------------------------------- bsdfs
-def roughconductor(d, eta, k, wi, u2, wo_eval):
-    """roughconductor.cpp:196-275 (sample), :277-345 (eval), :347-382 (pdf) -> (wo, pdf, weight[3]), eval[3], pdf"""
-    zero = np.zeros(3)
-    smp = (zero, 0.0, zero)
-    if wi[2] > 0:
-        m, pdf = d.sample(wi, u2)
-        wo = 2 * np.dot(wi, m) * m - wi
-        if pdf != 0 and wo[2] > 0:
-            w = d.g1(wo, m) if d.visible else d.G(wi, wo, m) * np.dot(wi, m) / (wi[2] * m[2])
-            smp = (wo, pdf / (4 * np.dot(wo, m)), fresnel_conductor(np.dot(wi, m), eta, k) * w)
-        else:
-            smp = (wo, pdf / (4 * np.dot(wo, m)) if np.dot(wo, m) != 0 else 0.0, zero)
-    ev, pd = zero, 0.0
-    if wi[2] > 0 and wo_eval[2] > 0:
-        h = wo_eval + wi
-        h /= np.linalg.norm(h)
-        D = d.eval(h)
-        if D != 0:
-            ev = fresnel_conductor(np.dot(wi, h), eta, k) * D * d.G(wi, wo_eval, h) / (4 * wi[2])
-        if np.dot(wi, h) > 0 and np.dot(wo_eval, h) > 0:
-            pd = D * d.g1(wi, h) / (4 * wi[2]) if d.visible else d.pdf(wi, h) / (4 * np.dot(wo_eval, h))
-    return smp, ev, pd
-
-
-def dielectric_sample(eta, wi, s1):
-    """dielectric.cpp:201-310, unpolarised, both lobes enabled, TransportMode::Radiance -> wo, pdf, eta, weight"""
-    r, cos_t, eta_it, eta_ti = fresnel(wi[2], eta)
-    if s1 <= r:
-        return np.array([-wi[0], -wi[1], wi[2]]), r, 1.0, 1.0, r
-    return np.array([-eta_ti * wi[0], -eta_ti * wi[1], cos_t]), 1 - r, eta_it, eta_ti * eta_ti, r
+from f64_integrators import (PI, Microfacet, cosine_hemisphere, dielectric_sample, disk_concentric, fresnel, fresnel_conductor,  # noqa: F401
+                             fresnel_diffuse_reflectance, hier2d_build, hier2d_sample, roughconductor, roughdielectric)
 
 
 def _bsdf_inputs(rng, n, upper=True):
@@ -462,14 +302,6 @@ def test_environment_map_against_float64_restatement(native, oracle):
     assert checked > 300
 
 
-def fresnel_diffuse_reflectance(eta):
-    """render/fresnel.h:327-362"""
-    if eta < 1:
-        return -1.4399 * eta * eta + 0.7099 * eta + 0.6681 + 0.0636 / eta
-    i = 1 / eta
-    return 0.919317 - 3.4793 * i + 6.75335 * i ** 2 - 7.80989 * i ** 3 + 4.98554 * i ** 4 - 1.36881 * i ** 5
-
-
 @pytest.mark.parametrize("nonlinear", [False, True])
 def test_plastic_and_conductor_against_float64_restatement(native, oracle, nonlinear):
     """plastic.cpp:161-290 (lobe choice by the Fresnel-weighted sampling weights of parameters_changed, :161-176; the diffuse
@@ -525,56 +357,6 @@ def test_plastic_and_conductor_against_float64_restatement(native, oracle, nonli
             assert _close(o[6:9], fresnel_conductor(wi[2], eta_c, k_c), 3e-5)
         else:
             assert not o[6:9].any()
-
-
-def roughdielectric(kind, au, av, visible, eta, wi, s1, u2, wo_eval):
-    """roughdielectric.cpp:203-310 (sample), :312-390 (eval), :392-447 (pdf); TransportMode::Radiance, both lobes enabled"""
-    ms = lambda v, s: v if s >= 0 else -v                         # enoki::mulsign on vectors / scalars
-    d = Microfacet(kind, au, av, visible)
-    ci = wi[2]
-    out_s = None
-    if ci != 0:
-        sd = Microfacet(kind, au, av, visible)
-        if not visible:
-            k = 1.2 - 0.2 * math.sqrt(abs(ci))
-            sd.au, sd.av = sd.au * k, sd.av * k                  # scale_alpha, microfacet.h:173-176
-        m, pdf = sd.sample(ms(wi, ci), u2)
-        if pdf != 0:
-            F, cos_t, eta_it, eta_ti = fresnel(float(np.dot(wi, m)), eta)
-            if s1 <= F:
-                wo = 2 * np.dot(wi, m) * m - wi
-                pdf *= F; bs_eta = 1.0; w = 1.0
-                dwh = 1 / (4 * np.dot(wo, m))
-            else:
-                wo = m * (np.dot(wi, m) * eta_ti + cos_t) - wi * eta_ti
-                pdf *= 1 - F; bs_eta = eta_it; w = eta_ti * eta_ti
-                dwh = (bs_eta ** 2 * np.dot(wo, m)) / (np.dot(wi, m) + bs_eta * np.dot(wo, m)) ** 2
-            w *= d.g1(wo, m) if visible else d.G(wi, wo, m) * np.dot(wi, m) / (ci * m[2])
-            out_s = (wo, pdf * abs(dwh), bs_eta, w, F)
-    ev = pd = 0.0
-    co = wo_eval[2]
-    if ci != 0:
-        refl = ci * co > 0
-        e, inv_e = (eta, 1 / eta) if ci > 0 else (1 / eta, eta)
-        m = wi + wo_eval * (1.0 if refl else e)
-        m /= np.linalg.norm(m)
-        m = ms(m, m[2])
-        D = d.eval(m)
-        F = fresnel(float(np.dot(wi, m)), eta)[0]
-        G = d.G(wi, wo_eval, m)
-        if refl:
-            ev = F * D * G / (4 * abs(ci))
-        else:
-            ev = abs((inv_e ** 2 * (1 - F) * D * G * e * e * np.dot(wi, m) * np.dot(wo_eval, m)) /
-                     (ci * (np.dot(wi, m) + e * np.dot(wo_eval, m)) ** 2))
-        if np.dot(wi, m) * ci > 0 and np.dot(wo_eval, m) * co > 0:
-            dwh = 1 / (4 * np.dot(wo_eval, m)) if refl else (e * e * np.dot(wo_eval, m)) / (np.dot(wi, m) + e * np.dot(wo_eval, m)) ** 2
-            sd = Microfacet(kind, au, av, visible)
-            if not visible:
-                k = 1.2 - 0.2 * math.sqrt(abs(ci))
-                sd.au, sd.av = sd.au * k, sd.av * k
-            pd = sd.pdf(ms(wi, ci), m) * (F if refl else 1 - F) * abs(dwh)
-    return out_s, ev, pd
 
 
 @pytest.mark.parametrize("kw", [
@@ -677,62 +459,6 @@ def test_spectral_leaves_against_float64_restatement(native, oracle_spectral):
         lam4, w4, sd4 = o[0:4], o[4:8], o[12:16]
         xyz = [np.mean([lerp_table(cie[c], lam4[k]) * w4[k] * sd4[k] for k in range(4)]) for c in range(3)]
         assert _close(o[16:19], xyz, 2e-5, 1e-12)
-
-
-def hier2d_build(data):
-    """Hierarchical2D<Float, 0> constructor, distr_2d.h:372-462 -> levels[0] = normalised data, levels[1..] = MIP hierarchy"""
-    h, w = data.shape
-    ny, nx = h - 1, w - 1
-    avg = 0.25 * (data[:-1, :-1] + data[:-1, 1:] + data[1:, :-1] + data[1:, 1:])
-    scale = nx * ny / avg.sum()
-    levels = [data * scale]
-
-    def pad(a):
-        return np.pad(a, ((0, a.shape[0] & 1), (0, a.shape[1] & 1)))
-    cur = pad(avg * scale)
-    levels.append(cur)
-    max_level = int(math.ceil(math.log2(max(nx, ny)))) if max(nx, ny) > 1 else 0
-    for _ in range(2, max_level + 2):
-        nxt = cur[0::2, 0::2] + cur[0::2, 1::2] + cur[1::2, 0::2] + cur[1::2, 1::2]
-        cur = pad(nxt) if max(nxt.shape) > 1 else nxt
-        levels.append(cur)
-    return levels, (nx, ny)
-
-
-def hier2d_sample(levels, npatch, u):
-    """Hierarchical2D::sample, distr_2d.h:473-556 + warp::square_to_bilinear / interval_to_linear, warp.h:359-407"""
-    sx, sy = min(max(u[0], 0.0), 1.0), min(max(u[1], 0.0), 1.0)
-    ox = oy = 0
-    for l in range(len(levels) - 2, 0, -1):
-        lv = levels[l]
-        ox, oy = ox * 2, oy * 2
-        # the four entries the reference fetches are consecutive in ITS storage (2 x 2 blocks, Level::index); here by coordinates
-        v00, v10, v01, v11 = lv[oy, ox], lv[oy, ox + 1], lv[oy + 1, ox], lv[oy + 1, ox + 1]
-        sx, sy = min(max(sx, 0.0), 1.0), min(max(sy, 0.0), 1.0)
-        r0, r1 = v00 + v10, v01 + v11
-        sy *= r0 + r1
-        m = sy > r0
-        if m:
-            oy += 1; sy -= r0
-        sy /= r1 if m else r0
-        c0, c1 = (v01, v11) if m else (v00, v10)
-        sx *= c0 + c1
-        m = sx > c0
-        if m:
-            sx -= c0; ox += 1
-        sx /= c1 if m else c0
-    d = levels[0]
-    v00, v10, v01, v11 = d[oy, ox], d[oy, ox + 1], d[oy + 1, ox], d[oy + 1, ox + 1]
-
-    def i2l(v0, v1, s):
-        if abs(v0 - v1) > 1e-4 * (v0 + v1):
-            return (v0 - math.sqrt(max(0.0, v0 * v0 + (v1 * v1 - v0 * v0) * s))) / (v0 - v1)
-        return s
-    r0, r1 = v00 + v10, v01 + v11
-    sy = i2l(r0, r1, sy)
-    c0, c1 = v00 + (v01 - v00) * sy, v10 + (v11 - v10) * sy
-    sx = i2l(c0, c1, sx)
-    return (ox + sx) / npatch[0], (oy + sy) / npatch[1], c0 + (c1 - c0) * sx
 
 
 @pytest.mark.parametrize("shape", [(5, 7), (2, 2), (9, 4), (17, 33)])
