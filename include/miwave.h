@@ -42,7 +42,9 @@ enum {
  * like ShapeKDTree::m_primitive_map (kdtree.h:2335-2353). */
 
 enum { MI_BSDF_DIFFUSE = 0, MI_BSDF_DIELECTRIC = 1, MI_BSDF_ROUGHCONDUCTOR = 2, MI_BSDF_CONDUCTOR = 3, MI_BSDF_PLASTIC = 4,
-       MI_BSDF_ROUGHDIELECTRIC = 5, MI_BSDF_ROUGHPLASTIC = 6 };
+       MI_BSDF_ROUGHDIELECTRIC = 5, MI_BSDF_ROUGHPLASTIC = 6,
+       MI_BSDF_THINDIELECTRIC = 7, MI_BSDF_NULL = 8,                       /* leaves with a Null lobe (wo = -wi)                    */
+       MI_BSDF_MASK = 9, MI_BSDF_BLEND = 10 };                             /* wrappers: their children are other records of `bsdfs` */
 enum { MI_BSDF_FLAG_GGX = 1, MI_BSDF_FLAG_SAMPLE_VISIBLE = 2,            /* roughconductor */
        MI_BSDF_FLAG_NONLINEAR = 1, MI_BSDF_FLAG_HAS_SPECULAR = 2,          /* plastic */
        MI_BSDF_FLAG_HAS_SPEC_REFLECTANCE = 4, MI_BSDF_FLAG_HAS_SPEC_TRANSMITTANCE = 8,   /* roughdielectric (+ GGX, SAMPLE_VISIBLE) */
@@ -95,16 +97,25 @@ typedef struct {
      * roughplastic (src/bsdfs/roughplastic.cpp:146-181,336-371): [0] alpha, [1] eta = int_ior/ext_ior, [2] 1/eta^2,
      *                                              [3] internal reflectance, [4] specular_sampling_weight, [5] (float) offset
      *                                              of its MI_ROUGH_TRANSMITTANCE_RES-entry external-transmittance table in
-     *                                              mi_scene_desc::bsdf_tables, [6..8] diffuse_reflectance, [9..11] specular_reflectance */
+     *                                              mi_scene_desc::bsdf_tables, [6..8] diffuse_reflectance, [9..11] specular_reflectance
+     * thindielectric (src/bsdfs/thindielectric.cpp:78-99): the layout of dielectric
+     * null (src/bsdfs/null.cpp):                    nothing
+     * mask (src/bsdfs/mask.cpp:68-91):              [0..2] opacity (three times), `back` = the nested record
+     * blendbsdf (src/bsdfs/blendbsdf.cpp:59-81):    [0..2] weight (three times), `back` = child 0, [3] = (float) index of child 1
+     * Nesting is one chain per record: [mask ->] [blendbsdf ->] leaf, where a leaf (each of a blend's two) may carry
+     * MI_BSDF_FLAG_TWOSIDED. mi_scene_upload refuses anything else (blend in blend, mask under blend, a wrapper with or under
+     * twosided, twosided around a Null or transmission lobe) with MI_ERR_INVALID and a message naming the record. */
     float params[14];
     /* scalar_spectral (and optionally scalar_rgb: used when tex[0].type != MI_TEX_RGB or params carry no colour):
      * diffuse: tex[0] reflectance; dielectric: tex[0] specular_reflectance, tex[1] specular_transmittance;
      * roughconductor / conductor: tex[0] eta, tex[1] k, tex[2] specular_reflectance; plastic: tex[0]
      * diffuse_reflectance, tex[1] specular_reflectance; roughdielectric: tex[0] specular_reflectance, tex[1]
-     * specular_transmittance. The scalar_rgb library derives these from params[] itself. */
+     * specular_transmittance; thindielectric: like dielectric; mask: tex[0] opacity; blendbsdf: tex[0] weight (both read
+     * through Texture::eval_1: a constant, a one-channel bitmap, or — scalar_rgb only — the luminance of a three-channel one).
+     * The scalar_rgb library derives the constants from params[] itself; a MI_TEX_BITMAP slot is taken as it is. */
     mi_texture tex[3];
     uint32_t back;        /* MI_BSDF_FLAG_TWOSIDED: index of the back side's record (its own index: same BSDF on both
-                             sides, src/bsdfs/twosided.cpp:72-73); else 0 */
+                             sides, src/bsdfs/twosided.cpp:72-73); mask: the nested record; blendbsdf: child 0; else 0 */
 } mi_bsdf;
 
 typedef struct {

@@ -138,6 +138,10 @@ class mi_sample_cfg(C.Structure):
 
 
 MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
+# mi_bsdf::type (include/miwave.h); MASK / BLEND are wrappers whose children are other records (mi_bsdf::back, params[3])
+(MI_BSDF_DIFFUSE, MI_BSDF_DIELECTRIC, MI_BSDF_ROUGHCONDUCTOR, MI_BSDF_CONDUCTOR, MI_BSDF_PLASTIC, MI_BSDF_ROUGHDIELECTRIC,
+ MI_BSDF_ROUGHPLASTIC, MI_BSDF_THINDIELECTRIC, MI_BSDF_NULL, MI_BSDF_MASK, MI_BSDF_BLEND) = range(11)
+MI_BSDF_FLAG_TWOSIDED = 0x100
 MI_BVH_FORCE_TREE, MI_BVH_NO_LEAF_FILTER, MI_BVH_RADIX_TREE = 0x10, 0x20, 0x40      # flags of mi_bvh_build's quality argument
 MI_OK, MI_ERR_INVALID, MI_ERR_DEVICE, MI_ERR_STATE, MI_ERR_CANCELLED = 0, -1, -2, -3, -4
 MI_EVAL = dict(PCG32=0, SINCOS=1, COSINE_HEMISPHERE=2, BSDF=3, FRESNEL=4, CAMERA_RAY=5, EMITTER_SAMPLE=6,
@@ -225,6 +229,7 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_props_set_lookat": (None, [vp, cp, c_float_p, c_float_p, c_float_p]),
         "mih_props_set_matrix": (None, [vp, cp, c_float_p]), "mih_rectangle_create": (vp, [vp]), "mih_sphere_create": (vp, [vp]),
         "mih_bsdf_create": (vp, [vp]), "mih_bsdf_destroy": (None, [vp]), "mih_bsdf_create_twosided": (vp, [vp, vp]),
+        "mih_bsdf_create_nested": (vp, [vp, C.POINTER(vp), u32]),
         "mih_fresnel_diffuse_reflectance": (C.c_float, [C.c_float]),
         "mih_bsdf_record": (i32, [vp, C.POINTER(mi_bsdf)]), "mih_bsdf_flags": (u32, [vp]),
         "mih_bsdf_table": (i32, [vp, c_float_p, u32]), "mih_gauss_legendre": (None, [i32, c_float_p, c_float_p]),

@@ -3,6 +3,9 @@
 struct SoaRays { const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt; };
 struct SoaHits { float *t, *u, *v; uint32_t *prim, *shape; };
 
+#ifndef MIW_KERNEL
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#endif
 template <bool AnyHit>
 __global__ __launch_bounds__(MIW_BLOCK) void k_trace_soa(SceneView sc, SoaRays R, SoaHits H, uint64_t n, TraceLds cfg) {
     extern __shared__ uint4 smem[];
@@ -22,7 +25,7 @@ __global__ __launch_bounds__(MIW_BLOCK) void k_trace_soa(SceneView sc, SoaRays R
 // ---- the Scene query surface (include/miwave.h: mi_ray_intersect, mi_sample_emitter_direction, ...) ----
 __device__ __forceinline__ void st3(float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; }
 
-__global__ __launch_bounds__(MIW_BLOCK) void k_ray_intersect(SceneView sc, SoaRays R, mi_surface_interaction *out, uint64_t n, TraceLds cfg) {
+MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_ray_intersect(SceneView sc, SoaRays R, mi_surface_interaction *out, uint64_t n, TraceLds cfg) {
     extern __shared__ uint4 smem[];
     stage_to_lds(sc, cfg, smem);
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(MIW_BLOCK) void k_ray_intersect(SceneView sc, SoaRa
     out[i] = r;
 }
 
-__global__ __launch_bounds__(MIW_BLOCK) void k_sample_emitter_direction(SceneView sc, int32_t emitter, const float *ref_p, const float *sample,
+MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_sample_emitter_direction(SceneView sc, int32_t emitter, const float *ref_p, const float *sample,
                                                                        const float *wavelengths, int test_visibility, mi_direction_sample *out,
                                                                        float *spec_out, uint64_t n, TraceLds cfg) {
     extern __shared__ uint4 smem[];
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(MIW_BLOCK) void k_sample_emitter_direction(SceneVie
     for (int k = 0; k < MIW_SPEC_N; ++k) spec_out[MIW_SPEC_N * i + k] = vf[k];
 }
 
-__global__ void k_pdf_emitter_direction(SceneView sc, int32_t emitter, const float *ref_p, const mi_direction_sample *ds, float *pdf, uint64_t n) {
+MIW_KERNEL void k_pdf_emitter_direction(SceneView sc, int32_t emitter, const float *ref_p, const mi_direction_sample *ds, float *pdf, uint64_t n) {
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const mi_direction_sample r = ds[i];
@@ -86,7 +89,7 @@ __global__ void k_pdf_emitter_direction(SceneView sc, int32_t emitter, const flo
     pdf[i] = v;
 }
 
-__global__ void k_emitter_eval(SceneView sc, const mi_surface_interaction *si, const float *wavelengths, float *spec_out, uint64_t n) {
+MIW_KERNEL void k_emitter_eval(SceneView sc, const mi_surface_interaction *si, const float *wavelengths, float *spec_out, uint64_t n) {
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Wavelengths wl;
@@ -106,7 +109,7 @@ __global__ void k_emitter_eval(SceneView sc, const mi_surface_interaction *si, c
     for (int k = 0; k < MIW_SPEC_N; ++k) spec_out[MIW_SPEC_N * i + k] = vf[k];
 }
 
-__global__ void k_eval(int op, RenderParams P, SceneView sc, const float *in, int is, float *out, int os, uint64_t n) {
+MIW_KERNEL void k_eval(int op, RenderParams P, SceneView sc, const float *in, int is, float *out, int os, uint64_t n) {
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *a = in + i * (uint64_t) is;

@@ -1,9 +1,12 @@
+#ifndef MIW_KERNEL
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#endif
 // Plan 2 (resident): k_init_pixels, the shared pixel queue and k_path_resident (path / direct integrators).
 // Part of the single translation unit csrc/miwave.hip (included there, in this order; not a stand-alone header).
 // ---- the resident plan -----------------------------------------------------------------
 // k_init_pixels: pixel <-> lane map and PCG32 seeding only (a pixel carries nothing else
 // between two camera samples).
-__global__ __launch_bounds__(MIW_BLOCK) void k_init_pixels(RenderParams P, U4 *st_out, uint32_t *pixel_out, InitArgs A) {
+MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_init_pixels(RenderParams P, U4 *st_out, uint32_t *pixel_out, InitArgs A) {
     uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= P.n_lanes) return;
     uint32_t tile = lane >> A.bs2_log2, i = lane & ((1u << A.bs2_log2) - 1u);
@@ -312,11 +315,11 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
             if (T.side) {
                 TileAdd add; add.tile = tile; add.x0 = tile_x0; add.y0 = tile_y0; add.side = (int) T.side;
                 SplatXYSink<TileAdd> sink; sink.film = &P.film; sink.add = add;
-                st = pixel_render<Integ>(P, sc, pixel, st, sample_end, tr2, sink, &local);
+                st = pixel_render<Integ, Mats == MATS_NESTED ? MATS_NESTED : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
             } else {
                 FilmAdd add; add.accum = accum;
                 SplatSink<FilmAdd> sink; sink.film = &P.film; sink.add = add;
-                st = pixel_render<Integ>(P, sc, pixel, st, sample_end, tr2, sink, &local);
+                st = pixel_render<Integ, Mats == MATS_NESTED ? MATS_NESTED : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
             }
             Q.st[lane] = st;
         }

@@ -64,7 +64,10 @@ __device__ __forceinline__ bool init_one_lane(const RenderParams &P, const LaneQ
     return P.spp > 0;
 }
 
-__global__ __launch_bounds__(MIW_BLOCK) void k_init_lanes(RenderParams P, LaneQueues Q, uint32_t *pixel_out, InitArgs A, WorkLists W) {
+#ifndef MIW_KERNEL
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#endif
+MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_init_lanes(RenderParams P, LaneQueues Q, uint32_t *pixel_out, InitArgs A, WorkLists W) {
     __shared__ uint32_t s_cnt[WL_LISTS];
     if (threadIdx.x < WL_LISTS) s_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -162,14 +165,14 @@ __global__ __launch_bounds__(MIW_BLOCK) void k_shade(RenderParams P, SceneView s
     if (mine) {
         if (UseLog && Q.log_rec) {                              // 16-byte records; the thresholds through L1 (plan 1 is not the fast path)
             LogSink16<const float *> sink{ Q.log_rec, Q.log_thr, &P.film, lane, P.spp, Q.log_rej & 255u, Q.log_rej >> 8 };
-            flags = lane_shade(P, sc, Q, lane, &local, sink);
+            flags = lane_shade<MATS_ALL>(P, sc, Q, lane, &local, sink);
         } else if (UseLog) {
             LogSink sink; sink.log_pos = Q.log_pos; sink.log_val = Q.log_val; sink.lane = lane; sink.spp = P.spp; sink.warn_negative = P.film.warn_negative;
-            flags = lane_shade(P, sc, Q, lane, &local, sink);
+            flags = lane_shade<MATS_ALL>(P, sc, Q, lane, &local, sink);
         } else {
             FilmAdd add; add.accum = accum;
             SplatSink<FilmAdd> sink; sink.film = &P.film; sink.add = add;
-            flags = lane_shade(P, sc, Q, lane, &local, sink);
+            flags = lane_shade<MATS_ALL>(P, sc, Q, lane, &local, sink);
         }
         active_lane = (!(flags & LF_DONE) && count_active) ? 1u : 0u;
     }

@@ -1,10 +1,11 @@
 // BSDF kernels on the path: smooth diffuse, smooth dielectric, rough conductor
 // (GGX / Beckmann microfacet with visible-normal sampling), smooth conductor, smooth plastic,
-// the two-sided adapter, plus Fresnel terms.
+// the two-sided adapter, the null / thin dielectric leaves, the mask / blend wrappers, plus Fresnel terms.
 //
 // Follows: src/bsdfs/diffuse.cpp:78-135, src/bsdfs/dielectric.cpp:201-320,
 // src/bsdfs/roughconductor.cpp:196-382, src/bsdfs/conductor.cpp:202-261, src/bsdfs/plastic.cpp:176-301,
-// src/bsdfs/twosided.cpp:94-172, include/mitsuba/render/microfacet.h:184-418,
+// src/bsdfs/twosided.cpp:94-172, src/bsdfs/null.cpp:44-71, src/bsdfs/thindielectric.cpp:95-160,
+// src/bsdfs/mask.cpp:93-150, src/bsdfs/blendbsdf.cpp:83-154, include/mitsuba/render/microfacet.h:184-418,
 // include/mitsuba/render/fresnel.h:34-116,275-294.
 // Unpolarized RGB only (the scalar_rgb variant); TransportMode::Radiance.
 #pragma once
@@ -18,6 +19,7 @@ namespace miw {
 
 // BSDFFlags subset (include/mitsuba/render/bsdf.h:40-124)
 enum : uint32_t {
+    BSDF_Null = 0x00001,
     BSDF_DiffuseReflection = 0x00002, BSDF_GlossyReflection = 0x00008, BSDF_GlossyTransmission = 0x00010,
     BSDF_Transmission = 0x00004 | 0x00010 | 0x00040,
     BSDF_DeltaReflection   = 0x00020, BSDF_DeltaTransmission = 0x00040,
@@ -27,7 +29,8 @@ enum : uint32_t {
 
 enum : uint32_t { BSDF_TYPE_DIFFUSE = 0, BSDF_TYPE_DIELECTRIC = 1, BSDF_TYPE_ROUGHCONDUCTOR = 2,
                   BSDF_TYPE_CONDUCTOR = 3, BSDF_TYPE_PLASTIC = 4, BSDF_TYPE_ROUGHDIELECTRIC = 5, BSDF_TYPE_ROUGHPLASTIC = 6,
-                  BSDF_TYPE_COUNT = 7 };
+                  BSDF_TYPE_THINDIELECTRIC = 7, BSDF_TYPE_NULL = 8, BSDF_TYPE_MASK = 9, BSDF_TYPE_BLEND = 10,
+                  BSDF_TYPE_COUNT = 11 };
 #define MIW_ROUGH_TRANSMITTANCE_RES 64      /* roughplastic.cpp:12 */
 // record flag bits: 0-1 belong to the type (roughconductor: GGX, sample_visible; plastic: nonlinear, has
 // specular_reflectance); bit 8 marks a record wrapped by the twosided adapter, whose back side is record `back`
@@ -52,20 +55,37 @@ enum : uint32_t { MF_BECKMANN = 0, MF_GGX = 1 };
 //                   the scene's table buffer (TexCtx::tables); tex[0] diffuse_reflectance, tex[1] specular_reflectance;
 //                   flags bit0 = GGX, bit1 = sample_visible, bit2 = specular_reflectance given, bit4 = nonlinear
 //   twosided:       the FRONT record with BSDF_REC_TWOSIDED set; `back` = table index of the back side's record
+//   thindielectric: p[0] eta, tex[0] specular_reflectance, tex[1] specular_transmittance (the slots of dielectric)
+//   null:           nothing
+//   mask:           tex[0] opacity (read through tex_eval_1), `back` = table index of the nested record
+//   blendbsdf:      tex[0] weight (tex_eval_1), `back` = table index of child 0, p[3] = (float) table index of child 1
+// A shape's record is one chain: [mask ->] [blendbsdf ->] leaf, the leaf (each of a blend's two) may be twosided; the uploader
+// refuses everything else, so that bsdf_side resolves a record without recursion.
 // (scalar_rgb callers may fill only p[] in the legacy layout — diffuse p[0..2]; dielectric p[1..3],
-//  p[4..6]; roughconductor p[2..4], p[5..7], p[8..10] — the uploader derives the TEX_RGB records.)
+//  p[4..6]; roughconductor p[2..4], p[5..7], p[8..10]; thindielectric like dielectric; mask / blendbsdf p[0..2] = the
+//  opacity / weight three times — the uploader derives the TEX_RGB records.)
 struct BsdfRec { uint32_t type, flags; float p[14]; TexRec tex[3]; uint32_t back; };
 
 struct BSDFSample { V3 wo; float pdf, eta; uint32_t sampled_type; };
 
 // texture slots a record of this type reads
 MIW_HD uint32_t bsdf_tex_slots(uint32_t type) {
-    return type == BSDF_TYPE_DIFFUSE ? 1u
-         : (type == BSDF_TYPE_DIELECTRIC || type == BSDF_TYPE_PLASTIC || type == BSDF_TYPE_ROUGHDIELECTRIC ||
+    return type == BSDF_TYPE_NULL ? 0u
+         : (type == BSDF_TYPE_DIFFUSE || type == BSDF_TYPE_MASK || type == BSDF_TYPE_BLEND) ? 1u
+         : (type == BSDF_TYPE_DIELECTRIC || type == BSDF_TYPE_THINDIELECTRIC || type == BSDF_TYPE_PLASTIC || type == BSDF_TYPE_ROUGHDIELECTRIC ||
             type == BSDF_TYPE_ROUGHPLASTIC) ? 2u : 3u;
 }
 
+// `Nested` = false compiles the null / thindielectric leaves and the wrappers out (see bsdf_side below). A wrapper record has no
+// lobes of its own: its flags are its children's (bsdf_side), plus Null for a mask.
+template <bool Nested = true>
 MIW_HD uint32_t bsdf_flags(const BsdfRec &b) {
+    if (Nested) {
+        if (b.type == BSDF_TYPE_THINDIELECTRIC) return BSDF_DeltaReflection | BSDF_Null;      // thindielectric.cpp:95-98
+        if (b.type == BSDF_TYPE_NULL) return BSDF_Null;                                         // null.cpp:38-39
+        if (b.type == BSDF_TYPE_MASK) return BSDF_Null;                                         // mask.cpp:89-90 (+ the nested flags)
+        if (b.type == BSDF_TYPE_BLEND) return 0u;                                               // blendbsdf.cpp:80
+    }
     switch (b.type) {
         case BSDF_TYPE_DIFFUSE:    return BSDF_DiffuseReflection;
         case BSDF_TYPE_DIELECTRIC: return BSDF_DeltaReflection | BSDF_DeltaTransmission;
@@ -618,11 +638,50 @@ MIW_HD Spec roughplastic_sample(const BsdfRec &b, V3 wi, float sample1, V2 sampl
     return roughplastic_eval(b, wi, bs.wo, tc) / bs.pdf;
 }
 
+// ---- Null (null.cpp:44-71) and ThinDielectric (thindielectric.cpp:101-160; both lobes enabled) ---------------------------
+MIW_HD Spec null_sample(V3 wi, BSDFSample &bs) {
+    bs.wo = v3(-wi.x, -wi.y, -wi.z); bs.pdf = 1.f; bs.eta = 1.f; bs.sampled_type = BSDF_Null;
+    return spec(1.f);
+}
+MIW_HD float thindielectric_reflectance(const BsdfRec &b, V3 wi) {
+    float r, ct, a, c;
+    fresnel(abs_(wi.z), b.p[0], r, ct, a, c);                        // :111
+    r *= 2.f / (1.f + r);                                            // :114, r' = r + trt + tr^3t + ..
+    return r;
+}
+MIW_HD Spec thindielectric_sample(const BsdfRec &b, V3 wi, float sample1, BSDFSample &bs, const TexCtx &tc) {
+    const float r = thindielectric_reflectance(b, wi), t = 1.f - r;
+    const bool selected_r = sample1 <= r;                            // :123
+    bs.pdf = selected_r ? r : t;
+    bs.wo = selected_r ? reflect(wi) : v3(-wi.x, -wi.y, -wi.z);      // :136
+    bs.eta = 1.f;
+    bs.sampled_type = selected_r ? BSDF_DeltaReflection : BSDF_Null;
+    return spec(1.f) * tex_eval(b.tex[selected_r ? 0 : 1], tc);      // :142-147 (an absent texture is the constant 1)
+}
+
+// Texture::eval_1 of a texture record: a constant is its value (uniform.cpp:42-45), a bitmap its interpolated value, the
+// luminance of that for three channels (bitmap.cpp:285-302; the uploader refuses those in scalar_spectral).
+MIW_HD float tex_eval_1(const TexRec &t, const TexCtx &tc) {
+    if (tc.bitmaps && t.type == TEX_BITMAP) {
+        const BitmapRec &bm = tc.bitmaps[(uint32_t) t.v[0]];
+        const Spec v = bitmap_eval(bm, tc.uv, tc.wl);
+#if MIW_SPECTRAL
+        return v.c[0];
+#else
+        if (bm.channels == 1) return v.x;
+        return v.x * 0.212671f + v.y * 0.715160f + v.z * 0.072169f;  // luminance(Color3f), spectrum.h
+#endif
+    }
+    return t.v[0];
+}
+MIW_HD float tex_eval_1_clamped(const TexRec &t, const TexCtx &tc) { return max_(min_(tex_eval_1(t, tc), 1.f), 0.f); }
+
 // Argument order matches BSDF::sample(ctx, si, sample1, sample2) (bsdf.h:328-340).
 // `Ext` = false compiles the plugins out that only scenes marked "extended" by the uploader contain (roughplastic).
 // `Trio` = true: the caller knows every record to be diffuse, dielectric or roughconductor (BASELINE configs 3 and 4):
 // the other plugins are compiled out — a kernel's code size is what its waves stream through the instruction cache.
-template <bool Ext = true, bool Trio = false>
+// `Nested` = false compiles the null and thindielectric leaves out (only scenes of the MATS_NESTED class hold them).
+template <bool Ext = true, bool Trio = false, bool Nested = true>
 MIW_HD Spec bsdf_sample(const BsdfRec &b, V3 wi, float sample1, V2 sample2, BSDFSample &bs, const TexCtx &tc) {
     if (Trio) {
         if (b.type == BSDF_TYPE_DIFFUSE) return diffuse_sample(b, wi, sample2, bs, tc);
@@ -630,6 +689,8 @@ MIW_HD Spec bsdf_sample(const BsdfRec &b, V3 wi, float sample1, V2 sample2, BSDF
         return roughconductor_sample(b, wi, sample2, bs, tc);
     }
     if (Ext && b.type == BSDF_TYPE_ROUGHPLASTIC) return roughplastic_sample(b, wi, sample1, sample2, bs, tc);
+    if (Nested && b.type == BSDF_TYPE_THINDIELECTRIC) return thindielectric_sample(b, wi, sample1, bs, tc);
+    if (Nested && b.type == BSDF_TYPE_NULL) return null_sample(wi, bs);
     switch (b.type) {
         case BSDF_TYPE_DIFFUSE:    return diffuse_sample(b, wi, sample2, bs, tc);
         case BSDF_TYPE_DIELECTRIC: return dielectric_sample(b, wi, sample1, bs, tc);
@@ -639,7 +700,7 @@ MIW_HD Spec bsdf_sample(const BsdfRec &b, V3 wi, float sample1, V2 sample2, BSDF
         default:                   return roughconductor_sample(b, wi, sample2, bs, tc);
     }
 }
-template <bool Ext = true, bool Trio = false>
+template <bool Ext = true, bool Trio = false, bool Nested = true>
 MIW_HD Spec bsdf_eval(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
     if (Trio) {
         if (b.type == BSDF_TYPE_DIFFUSE) return diffuse_eval(b, wi, wo, tc);
@@ -647,6 +708,7 @@ MIW_HD Spec bsdf_eval(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
         return roughconductor_eval(b, wi, wo, tc);
     }
     if (Ext && b.type == BSDF_TYPE_ROUGHPLASTIC) return roughplastic_eval(b, wi, wo, tc);
+    if (Nested && (b.type == BSDF_TYPE_THINDIELECTRIC || b.type == BSDF_TYPE_NULL)) return spec(0.f);   // thindielectric.cpp:152-155, null.cpp:63-66
     switch (b.type) {
         case BSDF_TYPE_DIFFUSE:    return diffuse_eval(b, wi, wo, tc);
         case BSDF_TYPE_DIELECTRIC: return spec(0.f);                 // dielectric.cpp:312-315
@@ -656,7 +718,7 @@ MIW_HD Spec bsdf_eval(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
         default:                   return roughconductor_eval(b, wi, wo, tc);
     }
 }
-template <bool Ext = true, bool Trio = false>
+template <bool Ext = true, bool Trio = false, bool Nested = true>
 MIW_HD float bsdf_pdf(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
     if (Trio) {
         if (b.type == BSDF_TYPE_DIFFUSE) return diffuse_pdf(wi, wo);
@@ -664,6 +726,7 @@ MIW_HD float bsdf_pdf(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
         return roughconductor_pdf(b, wi, wo);
     }
     if (Ext && b.type == BSDF_TYPE_ROUGHPLASTIC) return roughplastic_pdf(b, wi, wo, tc);
+    if (Nested && (b.type == BSDF_TYPE_THINDIELECTRIC || b.type == BSDF_TYPE_NULL)) return 0.f;         // thindielectric.cpp:157-160, null.cpp:68-71
     switch (b.type) {
         case BSDF_TYPE_DIFFUSE:    return diffuse_pdf(wi, wo);
         case BSDF_TYPE_DIELECTRIC: return 0.f;                       // dielectric.cpp:317-320
@@ -678,35 +741,121 @@ MIW_HD float bsdf_pdf(const BsdfRec &b, V3 wi, V3 wo, const TexCtx &tc) {
 // A shape's BSDF as the integrator sees it: the record itself, or — for a twosided record — the front
 // record when cos(theta_i) > 0, the back record with wi (and wo) mirrored when cos(theta_i) < 0 (:105-124),
 // nothing when cos(theta_i) == 0. `flags` is BSDF::flags() of the plugin (twosided: both sides, :76-86).
-struct BsdfSide { const BsdfRec *b; bool flip, none; uint32_t flags; };
-MIW_HD BsdfSide bsdf_side(const BsdfRec *table, uint32_t index, V3 wi) {
-    BsdfSide s; s.b = table + index; s.flip = false; s.none = false; s.flags = bsdf_flags(*s.b);
-    if (s.b->flags & BSDF_REC_TWOSIDED) {
-        const BsdfRec *back = table + s.b->back;
-        s.flags |= bsdf_flags(*back);
-        if (wi.z < 0.f) { s.flip = true; s.b = back; }
-        else if (!(wi.z > 0.f)) s.none = true;
+// `mask` / `blend`: the wrapper records in front of the leaf (nullptr: none); a blend's second child is `b1` with its own
+// `flip1` / `none1`. Only bsdf_side<true> fills these and only the <.., Nested = true> functions below read them.
+struct BsdfSide { const BsdfRec *b; bool flip, none; uint32_t flags; const BsdfRec *mask, *blend, *b1; bool flip1, none1; };
+// the twosided adapter of one leaf record: which record serves `wi`, mirrored or not; returns the plugin's flags
+template <bool Nested>
+MIW_HD uint32_t bsdf_leaf_side(const BsdfRec *table, const BsdfRec *&b, bool &flip, bool &none, V3 wi) {
+    flip = false; none = false;
+    uint32_t flags = bsdf_flags<Nested>(*b);
+    if (b->flags & BSDF_REC_TWOSIDED) {
+        const BsdfRec *back = table + b->back;
+        flags |= bsdf_flags<Nested>(*back);
+        if (wi.z < 0.f) { flip = true; b = back; }
+        else if (!(wi.z > 0.f)) none = true;
     }
+    return flags;
+}
+// `Nested` = false: the caller knows the table to hold neither wrappers nor the null / thindielectric leaves (every material
+// class of path.h but MATS_NESTED): none of that is compiled in. The default serves every table the uploader accepts.
+template <bool Nested = true>
+MIW_HD BsdfSide bsdf_side(const BsdfRec *table, uint32_t index, V3 wi) {
+    BsdfSide s; s.b = table + index;
+    if (Nested) {
+        s.mask = s.blend = s.b1 = nullptr; s.flip1 = s.none1 = false;
+        uint32_t wrapper_flags = 0;
+        if (s.b->type == BSDF_TYPE_MASK) { s.mask = s.b; s.b = table + s.b->back; wrapper_flags = BSDF_Null; }   // mask.cpp:89-90
+        if (s.b->type == BSDF_TYPE_BLEND) { s.blend = s.b; s.b1 = table + (uint32_t) s.b->p[3]; s.b = table + s.b->back; }
+        s.flags = bsdf_leaf_side<true>(table, s.b, s.flip, s.none, wi) | wrapper_flags;
+        if (s.blend) s.flags |= bsdf_leaf_side<true>(table, s.b1, s.flip1, s.none1, wi);                        // blendbsdf.cpp:80
+        return s;
+    }
+    s.flags = bsdf_leaf_side<false>(table, s.b, s.flip, s.none, wi);
     return s;
 }
 MIW_HD V3 bsdf_mirror(V3 w) { return v3(w.x, w.y, w.z * -1.f); }      // `wi.z() *= -1.f`
-template <bool Ext = true, bool Trio = false>
-MIW_HD Spec bsdf_side_sample(const BsdfSide &s, V3 wi, float sample1, V2 sample2, BSDFSample &bs, const TexCtx &tc) {
-    if (s.none) { bs.wo = v3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.sampled_type = 0; return spec(0.f); }
-    Spec v = bsdf_sample<Ext, Trio>(*s.b, s.flip ? bsdf_mirror(wi) : wi, sample1, sample2, bs, tc);
-    if (s.flip) bs.wo.z *= -1.f;                                     // :121
+template <bool Ext, bool Trio, bool Nested>
+MIW_HD Spec bsdf_leaf_sample(const BsdfRec *b, bool flip, bool none, V3 wi, float sample1, V2 sample2, BSDFSample &bs, const TexCtx &tc) {
+    if (none) { bs.wo = v3(0.f); bs.pdf = 0.f; bs.eta = 0.f; bs.sampled_type = 0; return spec(0.f); }
+    Spec v = bsdf_sample<Ext, Trio, Nested>(*b, flip ? bsdf_mirror(wi) : wi, sample1, sample2, bs, tc);
+    if (flip) bs.wo.z *= -1.f;                                       // :121
     return v;
 }
 // (one inlined copy of the plugin code each: the mirrored directions are selected first, not the results)
-template <bool Ext = true, bool Trio = false>
-MIW_HD Spec bsdf_side_eval(const BsdfSide &s, V3 wi, V3 wo, const TexCtx &tc) {
-    if (s.none) return spec(0.f);
-    return bsdf_eval<Ext, Trio>(*s.b, s.flip ? bsdf_mirror(wi) : wi, s.flip ? bsdf_mirror(wo) : wo, tc);
+template <bool Ext, bool Trio, bool Nested>
+MIW_HD Spec bsdf_leaf_eval(const BsdfRec *b, bool flip, bool none, V3 wi, V3 wo, const TexCtx &tc) {
+    if (none) return spec(0.f);
+    return bsdf_eval<Ext, Trio, Nested>(*b, flip ? bsdf_mirror(wi) : wi, flip ? bsdf_mirror(wo) : wo, tc);
 }
-template <bool Ext = true, bool Trio = false>
+template <bool Ext, bool Trio, bool Nested>
+MIW_HD float bsdf_leaf_pdf(const BsdfRec *b, bool flip, bool none, V3 wi, V3 wo, const TexCtx &tc) {
+    if (none) return 0.f;
+    return bsdf_pdf<Ext, Trio, Nested>(*b, flip ? bsdf_mirror(wi) : wi, flip ? bsdf_mirror(wo) : wo, tc);
+}
+// Scalar semantics of mask.cpp:93-130 and blendbsdf.cpp:83-124: the wrappers pick ONE child and rescale sample1 for it, so the
+// plugin code is still inlined once (the child is selected first, not its result) and the 0/0 of the untaken branch never exists.
+template <bool Ext = true, bool Trio = false, bool Nested = true>
+MIW_HD Spec bsdf_side_sample(const BsdfSide &s, V3 wi, float sample1, V2 sample2, BSDFSample &bs, const TexCtx &tc) {
+    const BsdfRec *b = s.b; bool flip = s.flip, none = s.none;
+    if (Nested) {
+        if (s.mask) {
+            const float opacity = tex_eval_1_clamped(s.mask->tex[0], tc);        // mask.cpp:110
+            if (!(sample1 < opacity)) {                                          // :114-121, the null lobe
+                bs.wo = v3(-wi.x, -wi.y, -wi.z); bs.eta = 1.f; bs.sampled_type = BSDF_Null; bs.pdf = 1.f - opacity;
+                return spec(1.f);
+            }
+            sample1 = sample1 / opacity;                                         // :123
+        }
+        if (s.blend) {
+            const float weight = tex_eval_1_clamped(s.blend->tex[0], tc);        // blendbsdf.cpp:90
+            if (sample1 > weight) sample1 = (sample1 - weight) / (1.f - weight); // :106, :110-111
+            else if (sample1 <= weight) { b = s.b1; flip = s.flip1; none = s.none1; sample1 = sample1 / weight; }   // :107, :117-118
+            else none = true;                                                    // (an unordered sample1: neither mask holds)
+        }
+    }
+    return bsdf_leaf_sample<Ext, Trio, Nested>(b, flip, none, wi, sample1, sample2, bs, tc);
+}
+template <bool Ext = true, bool Trio = false, bool Nested = true>
+MIW_HD Spec bsdf_side_eval(const BsdfSide &s, V3 wi, V3 wo, const TexCtx &tc) {
+    if (Nested && (s.mask || s.blend)) {
+        Spec r;
+        if (s.blend) {                                                           // blendbsdf.cpp:130, :141-142
+            const float weight = tex_eval_1_clamped(s.blend->tex[0], tc);
+            // c0 * (1 - weight) + c1 * weight, one inlined copy of the plugin code: the loop is kept rolled and carries the sum
+            r = spec(0.f);
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+            for (int i = 0; i < 2; ++i) {
+                const Spec c = bsdf_leaf_eval<Ext, Trio, Nested>(i ? s.b1 : s.b, i ? s.flip1 : s.flip, i ? s.none1 : s.none, wi, wo, tc);
+                r = i ? r + c * weight : c * (1.f - weight);
+            }
+        } else r = bsdf_leaf_eval<Ext, Trio, Nested>(s.b, s.flip, s.none, wi, wo, tc);
+        if (s.mask) r = r * tex_eval_1_clamped(s.mask->tex[0], tc);              // mask.cpp:136-137
+        return r;
+    }
+    return bsdf_leaf_eval<Ext, Trio, Nested>(s.b, s.flip, s.none, wi, wo, tc);
+}
+template <bool Ext = true, bool Trio = false, bool Nested = true>
 MIW_HD float bsdf_side_pdf(const BsdfSide &s, V3 wi, V3 wo, const TexCtx &tc) {
-    if (s.none) return 0.f;
-    return bsdf_pdf<Ext, Trio>(*s.b, s.flip ? bsdf_mirror(wi) : wi, s.flip ? bsdf_mirror(wo) : wo, tc);
+    if (Nested && (s.mask || s.blend)) {
+        float r;
+        if (s.blend) {                                                           // blendbsdf.cpp:157-159
+            const float weight = tex_eval_1_clamped(s.blend->tex[0], tc);
+            r = 0.f;
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+            for (int i = 0; i < 2; ++i) {
+                const float c = bsdf_leaf_pdf<Ext, Trio, Nested>(i ? s.b1 : s.b, i ? s.flip1 : s.flip, i ? s.none1 : s.none, wi, wo, tc);
+                r = i ? r + c * weight : c * (1.f - weight);
+            }
+        } else r = bsdf_leaf_pdf<Ext, Trio, Nested>(s.b, s.flip, s.none, wi, wo, tc);
+        if (s.mask) r *= tex_eval_1_clamped(s.mask->tex[0], tc);                 // mask.cpp:151-153
+        return r;
+    }
+    return bsdf_leaf_pdf<Ext, Trio, Nested>(s.b, s.flip, s.none, wi, wo, tc);
 }
 
 } // namespace miw

@@ -27,7 +27,7 @@ MIW_HD bool direct_primary(const RenderParams &P, const SceneView &sc, LaneRegs 
     int32_t emitter = -1;
     uint32_t bsdf_index = 0;
     if (valid) {
-        hit_surface_interaction<Analytic, Mats == MATS_ALL>(sc, f2u(h.w), h.x, h.y, h.z, [ray_o]() { return ray_o; }, ray_d, si, bsdf_index, emitter);
+        hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h.w), h.x, h.y, h.z, [ray_o]() { return ray_o; }, ray_d, si, bsdf_index, emitter);
         L.flags |= LF_VALID_RAY;                                  // :114
     }
     else if (sc.env) emitter = (int32_t) sc.env->emitter_index;  // scene.h:248-249
@@ -35,7 +35,7 @@ MIW_HD bool direct_primary(const RenderParams &P, const SceneView &sc, LaneRegs 
         L.res = L.res + (valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : env_eval_spec(*sc.env, ray_d, L.wl));
     if (!valid) return false;                                     // :125-127
     if (cnt_local) cnt_local->segments++;
-    bsdf = bsdf_side(sc.bsdfs, bsdf_index, si.wi);                // :132
+    bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);                // :132
     L.ray.o = si.p; L.ray.mint = spawn_mint(si.p);                // every further ray leaves from here
     L.ray.d = v3(0.f); L.ray.maxt = -1.f;
     return true;
@@ -50,9 +50,9 @@ MIW_HD bool direct_emitter_sample(const RenderParams &P, const SceneView &sc, La
     Spec emitter_val = sample_emitter_direction<Analytic>(sc, si.p, next_2d(L.rng), ds, L.wl);   // :141-142
     if (ds.pdf == 0.f) return false;                              // :143-145
     V3 wo = to_local(si.sh, ds.d);                                // :148
-    const TexCtx tc(L.wl, si.uv, Mats == MATS_ALL ? sc.bitmaps : nullptr, Mats == MATS_ALL ? sc.bsdf_tables : nullptr);
-    Spec bsdf_val = bsdf_side_eval<Mats == MATS_ALL>(bsdf, si.wi, wo, tc);   // :150
-    float bsdf_pdf = bsdf_side_pdf<Mats == MATS_ALL>(bsdf, si.wi, wo, tc);   // :155
+    const TexCtx tc(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr, mats_full(Mats) ? sc.bsdf_tables : nullptr);
+    Spec bsdf_val = bsdf_side_eval<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, wo, tc);   // :150
+    float bsdf_pdf = bsdf_side_pdf<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, wo, tc);   // :155
     float mis = mis_weight(ds.pdf * D.frac_lum, bsdf_pdf * D.frac_bsdf) * D.weight_lum;   // :157-158 (no delta emitters)
     Spec c = mis * bsdf_val * emitter_val;                        // :159
     if (all_zero(c)) return false;
@@ -67,8 +67,8 @@ MIW_HD bool direct_bsdf_sample(const SceneView &sc, LaneRegs &L, const SurfaceIn
     float s1 = next_1d(L.rng);                                    // :166-167 (Clang order: next_1d, then next_2d)
     V2 s2 = next_2d(L.rng);
     BSDFSample bs;
-    pend.bsdf_val = bsdf_side_sample<Mats == MATS_ALL>(bsdf, si.wi, s1, s2, bs, TexCtx(L.wl, si.uv, Mats == MATS_ALL ? sc.bitmaps : nullptr,
-                                                                                   Mats == MATS_ALL ? sc.bsdf_tables : nullptr));
+    pend.bsdf_val = bsdf_side_sample<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, s1, s2, bs, TexCtx(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr,
+                                                                                   mats_full(Mats) ? sc.bsdf_tables : nullptr));
     if (all_zero(pend.bsdf_val)) return false;                    // :170
     pend.pdf = bs.pdf; pend.delta = (bs.sampled_type & BSDF_Delta) != 0;
     L.ray.d = to_world(si.sh, bs.wo);                             // :173-174, interaction.h:58-61
@@ -181,8 +181,8 @@ MIW_HD void pixel_stream_render_direct(const RenderParams &P, const SceneView &s
                     }
                     if (ie == n_emitter && ib == n_bsdf) break;
                     int32_t emitter; uint32_t bsdf_index;              // more samples from this point: the interaction again
-                    hit_surface_interaction<Analytic, Mats == MATS_ALL>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
-                    bsdf = bsdf_side(sc.bsdfs, bsdf_index, si.wi);
+                    hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
+                    bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
                 }
             }
         }
@@ -227,8 +227,8 @@ MIW_HD void direct_sample_ray(const RenderParams &P, const SceneView &sc, LaneRe
                 }
                 if (ie == n_emitter && ib == n_bsdf) break;
                 int32_t emitter; uint32_t bsdf_index;              // more samples from this point: the interaction again
-                hit_surface_interaction<Analytic, Mats == MATS_ALL>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
-                bsdf = bsdf_side(sc.bsdfs, bsdf_index, si.wi);
+                hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
+                bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
             }
         }
     }

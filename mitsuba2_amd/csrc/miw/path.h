@@ -312,7 +312,11 @@ enum { STEP_CONTINUE = 0,        // extension ray queued in L.ray
 // smooth diffuse: BASELINE config 2) carries no dispatch and none of the other plugins' code; MATS_ALL is the table;
 // MATS_PLAIN is the table for scenes without texture coordinates and bitmap textures (the lookups compiled out).
 // MATS_TRIO is MATS_PLAIN for scenes whose records are all diffuse / dielectric / roughconductor (BASELINE configs 3, 4).
-enum { MATS_ALL = 0, MATS_DIFFUSE = 1, MATS_PLAIN = 2, MATS_TRIO = 3 };
+// MATS_NESTED is MATS_ALL plus the mask / blendbsdf wrappers and the null / thindielectric leaves (bsdf.h: bsdf_side<true>): the
+// class of scenes whose table holds one of those four; the other classes compile all of that out. It is also the default of the
+// entry points the CPU checker calls (lane_shade, pixel_render), which serve every table.
+enum { MATS_ALL = 0, MATS_DIFFUSE = 1, MATS_PLAIN = 2, MATS_TRIO = 3, MATS_NESTED = 4 };
+MIW_HD constexpr bool mats_full(int mats) { return mats == MATS_ALL || mats == MATS_NESTED; }   // texture coordinates, bitmaps, extended plugins
 // `Analytic` = false compiles the analytic-shape branch out (scenes the caller knows to be triangles only).
 template <int Mats = MATS_ALL, bool Analytic = true, typename PrevO, typename Cnt>
 MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4 h, PrevO prev_o,
@@ -327,7 +331,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     uint32_t bsdf_index = 0;
     int32_t emitter = -1;                            // scene.h:243-253 (no environment emitter)
     // only MATS_ALL kernels are launched for scenes with texture coordinates (miwave.hip: diffuse_only / textured)
-    if (valid) hit_surface_interaction<Analytic, Mats == MATS_ALL>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
+    if (valid) hit_surface_interaction<Analytic, mats_full(Mats)>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
     else if (sc.env) emitter = (int32_t) sc.env->emitter_index;   // a miss sees the environment, scene.h:248-249
     if (depth == 1 && valid) L.flags |= LF_VALID_RAY;   // path.cpp:121
     MIW_SECTION(7);                                   // (sections 6.. : the shade body of the phase machine, debug builds)
@@ -371,15 +375,16 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     if (cnt_local) cnt_local->segments++;
     BsdfSide bsdf;                                                   // si.bsdf(ray), incl. the twosided adapter
     if (Mats == MATS_DIFFUSE) { bsdf.b = sc.bsdfs + bsdf_index; bsdf.flip = bsdf.none = false; bsdf.flags = BSDF_DiffuseReflection; }
-    else bsdf = bsdf_side(sc.bsdfs, bsdf_index, si.wi);
+    else bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
     const uint32_t bflags = bsdf.flags;
     L.ray.o = si.p; L.ray.mint = spawn_mint(si.p);   // shared by shadow + extension ray
     L.ray.d = v3(0.f); L.ray.maxt = -1.f;
 
     // what the plugin's texture lookups see of `si`; only MATS_ALL kernels are launched for scenes with bitmap textures
-    const TexCtx tc(L.wl, si.uv, Mats == MATS_ALL ? sc.bitmaps : nullptr, Mats == MATS_ALL ? sc.bsdf_tables : nullptr);
-    constexpr bool Ext = Mats == MATS_ALL;           // plugins only "extended" scenes contain (roughplastic)
+    const TexCtx tc(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr, mats_full(Mats) ? sc.bsdf_tables : nullptr);
+    constexpr bool Ext = mats_full(Mats);            // plugins only "extended" scenes contain (roughplastic)
     constexpr bool Trio = Mats == MATS_TRIO;
+    constexpr bool Nested = Mats == MATS_NESTED;     // wrapper resolution, null / thindielectric
 
     // ---- emitter sampling, :155-172 ----
     if (bflags & BSDF_Smooth) {
@@ -387,8 +392,8 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
         Spec emitter_val = sample_emitter_direction<Analytic>(sc, si.p, next_2d(L.rng), ds, L.wl);
         if (ds.pdf != 0.f) {
             V3 wo = to_local(si.sh, ds.d);
-            Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_eval(*bsdf.b, si.wi, wo, tc) : bsdf_side_eval<Ext, Trio>(bsdf, si.wi, wo, tc);
-            float bpdf = Mats == MATS_DIFFUSE ? diffuse_pdf(si.wi, wo) : bsdf_side_pdf<Ext, Trio>(bsdf, si.wi, wo, tc);
+            Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_eval(*bsdf.b, si.wi, wo, tc) : bsdf_side_eval<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
+            float bpdf = Mats == MATS_DIFFUSE ? diffuse_pdf(si.wi, wo) : bsdf_side_pdf<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
             float mis = mis_weight(ds.pdf, bpdf);
             Spec c = mis * L.tp * bsdf_val * emitter_val;
             if (!all_zero(c)) {
@@ -404,7 +409,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     float s1 = next_1d(L.rng);
     V2 s2 = next_2d(L.rng);
     BSDFSample bs;
-    Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_sample(*bsdf.b, si.wi, s2, bs, tc) : bsdf_side_sample<Ext, Trio>(bsdf, si.wi, s1, s2, bs, tc);
+    Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_sample(*bsdf.b, si.wi, s2, bs, tc) : bsdf_side_sample<Ext, Trio, Nested>(bsdf, si.wi, s1, s2, bs, tc);
     L.tp = L.tp * bsdf_val;
     if (all_zero(L.tp))                              // :182-184
         return sh.has ? STEP_DEAD_PENDING : STEP_FINISHED;
@@ -423,7 +428,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
 // Returns the lane's new flag word: LF_DONE clear = the lane still has work; LF_RAY_ACTIVE = an
 // extension / primary ray is queued; LF_HAS_SHADOW = a shadow ray is queued; LF_DEAD_PENDING = the
 // sample only waits for that shadow ray (the device builds the next iteration's work lists from these).
-template <typename Sink, typename Cnt>
+template <int Mats = MATS_NESTED, typename Sink, typename Cnt>
 MIW_HD uint32_t lane_shade(const RenderParams &P, const SceneView &sc, const LaneQueues &Q,
                            uint32_t lane, Cnt *cnt_local, Sink sink) {
     LaneRegs L;
@@ -447,7 +452,7 @@ MIW_HD uint32_t lane_shade(const RenderParams &P, const SceneView &sc, const Lan
         F4 rd = Q.ray_d[lane];
         L.ray.d = v3(rd.x, rd.y, rd.z);
         ShadowOut sh;
-        const int r = path_step(P, sc, L, Q.hit[lane],
+        const int r = path_step<Mats>(P, sc, L, Q.hit[lane],
                                 [&]() { F4 ro = Q.ray_o[lane]; return v3(ro.x, ro.y, ro.z); }, sh, cnt_local);
         if (sh.has) {
             F4 sd; sd.x = sh.d.x; sd.y = sh.d.y; sd.z = sh.d.z; sd.w = sh.maxt;
@@ -590,7 +595,7 @@ MIW_HD void pixel_stream_render_direct(const RenderParams &P, const SceneView &s
                                        Trace2 trace2, Cnt *cnt_local);     // direct.h
 
 // One pixel, samples [st.w, sample_end): returns the updated st word.
-template <uint32_t Integ = INTEG_PATH, typename Trace2, typename Sink, typename Cnt>
+template <uint32_t Integ = INTEG_PATH, int Mats = MATS_NESTED, typename Trace2, typename Sink, typename Cnt>
 MIW_HD U4 pixel_render(const RenderParams &P, const SceneView &sc, uint32_t pixel, U4 st, uint32_t sample_end,
                        Trace2 trace2, Sink sink, Cnt *cnt_local) {
     struct OnePixel {
@@ -602,8 +607,8 @@ MIW_HD U4 pixel_render(const RenderParams &P, const SceneView &sc, uint32_t pixe
         MIW_HD void tick(uint32_t, bool) { }
         MIW_HD void put(uint32_t px, uint32_t sample_idx, V2 pos, const float *aovs) { sink(px, sample_idx, pos, aovs); }
     } work{ pixel, st, false, sink };
-    if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<MATS_ALL, true>(P, sc, sample_end, work, trace2, cnt_local);
-    else pixel_stream_render(P, sc, sample_end, work, trace2, cnt_local);
+    if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<Mats, true>(P, sc, sample_end, work, trace2, cnt_local);
+    else pixel_stream_render<Mats>(P, sc, sample_end, work, trace2, cnt_local);
     return work.st;
 }
 

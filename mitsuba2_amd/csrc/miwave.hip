@@ -1,4 +1,5 @@
-// libmiwave.so — gfx950 kernels and the C ABI declared in include/miwave.h. One translation unit:
+// libmiwave.so — gfx950 kernels and the C ABI declared in include/miwave.h. One translation unit (the build compiles the kernels of
+// one material class beside it, device/nested_instances.h):
 //   miw/*.h                      leaf arithmetic shared with the CPU checker (float32, fixed operation order)
 //   device/trace.h               LDS staging, packet sweep + leaf filter, LDS-stack BVH walk, trace2
 //   device/wavefront_kernels.h   plan 1: k_init_lanes, k_trace<closest|any>, k_shade over SoA queues in HBM
@@ -56,6 +57,11 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "miw/bvh.h"
 #include "miw/path.h"
 #include "miw/direct.h"
+#if defined(MIW_NESTED_PART)            /* miwave_nested.hip: the path kernels alone (device/nested_instances.h); the library's other kernels have one definition, here */
+#include "miw/bvh4.h"
+#include "miw/bvh8.h"
+#define MIW_KERNEL static __global__    /* ... and those of their headers that are no templates stay out of its objects */
+#else
 #include "rect_build.h"
 #include "miw/film_gather.h"
 #include "texture_build.h"
@@ -68,6 +74,7 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "bvh4_device.h"
 #include "bvh8_device.h"
 #include "film_reduce.h"
+#endif
 
 using namespace miw;
 
@@ -89,14 +96,18 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/wavefront_kernels.h"
 #include "device/resident_kernel.h"
 #include "device/phased_kernel.h"
+#if !defined(MIW_NESTED_PART)
 #if !MIW_SPECTRAL
 #include "device/pooled_kernel.h"      /* (experimental, opt-in: the scalar_rgb library only) */
 #endif
 #include "device/stream_trace.h"
 #include "device/film_kernels.h"
+#endif
 #include "device/eval_kernels.h"
 #include "device/sample_kernel.h"
+#include "device/nested_instances.h"   /* a split build (-DMIW_SPLIT_NESTED=1) compiles the MATS_NESTED kernels in miwave_nested.hip */
 
+#if !defined(MIW_NESTED_PART)           /* (miwave_nested.hip includes this file for the kernels above alone) */
 __global__ void k_iota(uint32_t *out, uint32_t n) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = i; }
 
 // ---------------------------------------------------------------------------------------
@@ -199,6 +210,7 @@ struct mi_ctx {
     std::vector<AnalyticRec> rects;                 // analytic rectangles
     std::vector<BsdfRec> bsdfs; bool diffuse_only = false;   // every record one-sided smooth diffuse
     bool trio = false;                                       // every record diffuse / dielectric / roughconductor: MATS_TRIO kernels
+    bool nested = false;                                     // a mask / blendbsdf / null / thindielectric record: MATS_NESTED kernels (textured is set too)
     bool textured = false;                                   // texture coordinates, bitmaps or an "extended" plugin: MATS_ALL kernels
     std::vector<float> bsdf_tables; DevBuf<float> d_bsdf_tables;
     std::vector<EmitterRec> emitters;
@@ -510,18 +522,11 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
         if (s->bsdf_table_floats && !s->bsdf_tables) return fail(c, MI_ERR_INVALID, "scene: bsdf_table_floats without bsdf_tables");
         if (const char *why = bsdf_record_from_abi(b, s->bitmap_count, s->bsdf_table_floats, r, &slot))
             return slot < 0 ? fail(c, MI_ERR_INVALID, "bsdf %u: %s", i, why) : fail(c, MI_ERR_INVALID, "bsdf %u: texture %d: %s", i, slot, why);
-        r.back = 0;
-        if (b.flags & MI_BSDF_FLAG_TWOSIDED) {                 // twosided.cpp:62-92
-            if (b.back >= s->bsdf_count) return fail(c, MI_ERR_INVALID, "bsdf %u: back-side record %u out of range", i, b.back);
-            const uint32_t tr = BSDF_Transmission;
-            BsdfRec probe; memset(&probe, 0, sizeof probe);
-            probe.type = b.type; const uint32_t f0 = bsdf_flags(probe);
-            probe.type = s->bsdfs[b.back].type; const uint32_t f1 = probe.type < BSDF_TYPE_COUNT ? bsdf_flags(probe) : 0u;
-            if ((f0 | f1) & tr) return fail(c, MI_ERR_INVALID, "bsdf %u: only materials without a transmission component can be nested", i);
-            r.back = b.back;
-        }
+        if (!(b.flags & MI_BSDF_FLAG_TWOSIDED) && b.type != BSDF_TYPE_MASK && b.type != BSDF_TYPE_BLEND) r.back = 0;
         c->bsdfs[i] = r;
     }
+    for (uint32_t i = 0; i < s->bsdf_count; ++i)               // twosided.cpp:62-92 and the chain rule of the wrappers
+        if (const char *why = bsdf_chain_check(c->bsdfs, i, s->bitmaps)) return fail(c, MI_ERR_INVALID, "bsdf %u: %s", i, why);
     c->diffuse_only = true;
     for (const BsdfRec &r : c->bsdfs) if (r.type != BSDF_TYPE_DIFFUSE || (r.flags & BSDF_REC_TWOSIDED)) c->diffuse_only = false;
     if (!c->tri_uv_in.empty()) c->diffuse_only = false;          // texture coordinates steer the shading frame (mesh.cpp:492-511)
@@ -544,6 +549,8 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     for (const BsdfRec &r : c->bsdfs) if (r.type != BSDF_TYPE_DIFFUSE && r.type != BSDF_TYPE_DIELECTRIC && r.type != BSDF_TYPE_ROUGHCONDUCTOR) c->trio = false;
     c->textured = !c->tri_uv_in.empty();
     for (const BsdfRec &r : c->bsdfs) if (bsdf_uses_bitmap(r) || bsdf_is_extended(r)) c->textured = true;   // -> the MATS_ALL kernels
+    c->nested = false;
+    for (const BsdfRec &r : c->bsdfs) if (bsdf_is_nested(r)) c->nested = c->textured = true;                // -> the MATS_NESTED kernels
     c->bsdf_tables.assign(s->bsdf_tables, s->bsdf_tables + s->bsdf_table_floats);
     HIP_TRY(c, c->d_bsdf_tables.upload(c->bsdf_tables, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1213,13 +1220,17 @@ static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO 
     // the instantiation mi_render would pick for this scene: no BSDF dispatch when every shape is plain diffuse, no texture lookups
     // without texture coordinates, no analytic shapes where there are none
     if (direct) {
-        if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_DIRECT);
+        if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_DIRECT);
+        else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_DIRECT);
+        else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_DIRECT);
         else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_DIRECT);
         else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_DIRECT);
         else MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, true, INTEG_DIRECT);
     }
     else if (tiny && c->diffuse_only && small) MIW_SAMPLE_LAUNCH(2, MATS_DIFFUSE, false, INTEG_PATH);
     else if (tiny && c->diffuse_only) MIW_SAMPLE_LAUNCH(1, MATS_DIFFUSE, false, INTEG_PATH);
+    else if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_PATH);
+    else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_PATH);
     else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_PATH);
     else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_PATH);
     else if (tiny && small) MIW_SAMPLE_LAUNCH(2, MATS_PLAIN, false, INTEG_PATH);
@@ -1820,7 +1831,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     const bool lds_resident = c->lds_cfg.brute || (c->lds_cfg.nodes_staged >= c->view.node_count && c->lds_cfg.tris_staged >= c->view.tri_count);
     // measured on MI355X: the resident plan wins whenever the scene query runs out of LDS
     // (packets / staged tree) or with the LDS-stack walk; the queue plan remains for the stackless fallback
-    if (plan == 0) plan = (lds_resident || c->lds_cfg.stack) ? 2 : 1;
+    if (plan == 0) plan = (lds_resident || c->lds_cfg.stack || c->nested) ? 2 : 1;
+    if (plan == 1 && c->nested) return fail(c, MI_ERR_INVALID, "render: scenes with mask / blendbsdf / null / thindielectric records run the resident plan only (plan 0 or 2)");
 #if MIW_SPECTRAL
     if (cfg->plan == 1) return fail(c, MI_ERR_INVALID, "render: the scalar_spectral library runs the resident plan only (plan 0 or 2)");
     plan = 2;
@@ -2037,6 +2049,10 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_ALL, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_ALL, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
             }
         }
         const uint32_t sync_every = 8;
@@ -2194,7 +2210,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #define MIW_POOLED_LAUNCH_(M, A, NW_, PP_) do { HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
                                      MIW_TIMED(6, hipLaunchKernelGGL((k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } while (0)
 #define MIW_POOLED_LAUNCH(M, A) do { if (pool_pp == 2) MIW_POOLED_LAUNCH_(M, A, 8, 2); else MIW_POOLED_LAUNCH_(M, A, 12, 1); } while (0)
-                    if (c->textured) MIW_POOLED_LAUNCH_(MATS_ALL, true, 12, 1);
+                    if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
+                    else if (c->textured) MIW_POOLED_LAUNCH_(MATS_ALL, true, 12, 1);
                     else if (trio_kernel) MIW_POOLED_LAUNCH(MATS_TRIO, false);
                     else if (c->rects.empty()) MIW_POOLED_LAUNCH_(MATS_PLAIN, false, 12, 1);
                     else MIW_POOLED_LAUNCH_(MATS_PLAIN, true, 12, 1);
@@ -2205,22 +2222,26 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #endif
                 else
                 if (phased8 && place) {
-                    if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, true);
+                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, true);
+                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, true);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, true);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, true);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, true);
                 } else if (phased8) {
-                    if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, false);
+                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, false);
+                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, false);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, false);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, false);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, false);
                 } else if (phased && place) {                           // a shard of about one pixel per resident lane: the Placed instantiations (measuring, then placed launch)
-                    if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 1, true);
+                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 1, true);
+                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 1, true);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 1, true);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 1, true);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 1, true);
                 } else if (phased) {
                     if (!c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);
+                    else if (c->nested) MIW_PHASED_LAUNCH(MATS_NESTED, true, 1);
                     else if (c->textured) MIW_PHASED_LAUNCH(MATS_ALL, true, 1);
                     else if (trio_kernel) MIW_PHASED_LAUNCH(MATS_TRIO, false, 1);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH(MATS_PLAIN, false, 1);
@@ -2230,7 +2251,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #undef MIW_PHASED_LAUNCH_
                 else if (direct) {
 #define MIW_DIRECT_LAUNCH(T, M, A) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, INTEG_DIRECT>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
-                    if (tiny && c->textured) MIW_DIRECT_LAUNCH(1, MATS_ALL, false);
+                    if (tiny && c->nested) MIW_DIRECT_LAUNCH(1, MATS_NESTED, false);
+                    else if (c->nested) MIW_DIRECT_LAUNCH(0, MATS_NESTED, true);
+                    else if (tiny && c->textured) MIW_DIRECT_LAUNCH(1, MATS_ALL, false);
                     else if (tiny) MIW_DIRECT_LAUNCH(1, MATS_PLAIN, false);
                     else if (c->textured) MIW_DIRECT_LAUNCH(0, MATS_ALL, true);
                     else MIW_DIRECT_LAUNCH(0, MATS_PLAIN, true);
@@ -2244,6 +2267,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (tiny && c->diffuse_only && c->view.tri_count <= 32u) MIW_PATH_LAUNCH(2, MATS_DIFFUSE);   // 32-bit candidate masks (BASELINE config 2: 32 triangles)
                 else if (tiny && c->diffuse_only) MIW_PATH_LAUNCH(1, MATS_DIFFUSE);
+                else if (tiny && c->nested) MIW_PATH_LAUNCH(1, MATS_NESTED);          // + wrapper resolution, null / thindielectric
+                else if (c->nested) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_NESTED, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (tiny && c->textured) MIW_PATH_LAUNCH(1, MATS_ALL);           // texture coordinates / bitmap lookups compiled in
                 else if (!tiny && c->textured) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_ALL, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (tiny && c->view.tri_count <= 32u) MIW_PATH_LAUNCH(2, MATS_PLAIN);
@@ -2251,7 +2276,15 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 else if (c->rects.empty()) MIW_PATH_LAUNCH(0, MATS_PLAIN);
                 else MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_PLAIN, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
 #undef MIW_PATH_LAUNCH
-            } else if (direct && tiny)
+            } else if (c->nested && direct && tiny)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->nested && direct)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->nested && tiny)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->nested)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (direct && tiny)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_ALL, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
             else if (direct)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_ALL, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
@@ -2447,3 +2480,4 @@ mi_status mi_selftest(mi_ctx *c, int32_t which, uint64_t *mismatches) {
 }
 
 } // extern "C"
+#endif // !MIW_NESTED_PART

@@ -59,12 +59,18 @@ inline const char *bsdf_record_from_abi(const mi_bsdf &b, uint32_t bitmap_count,
     std::memcpy(r.p, b.params, sizeof r.p);
     *bad = -1;
     if (b.type >= BSDF_TYPE_COUNT) return "unknown type";
+    if (b.type == BSDF_TYPE_MASK || b.type == BSDF_TYPE_BLEND) {
+        if (b.flags & MI_BSDF_FLAG_TWOSIDED) return "a mask / blendbsdf record cannot carry MI_BSDF_FLAG_TWOSIDED (wrap its children instead)";
+        const float o = b.params[3];
+        if (b.type == BSDF_TYPE_BLEND && (!(o >= 0.f) || o != (float) (uint32_t) o)) return "blendbsdf: params[3] is not the index of its second child";
+    }
     if (b.type == BSDF_TYPE_ROUGHPLASTIC) {
         const float o = b.params[5];
         if (!(o >= 0.f) || o != (float) (uint32_t) o || (uint64_t) o + MI_ROUGH_TRANSMITTANCE_RES > table_floats)
             return "roughplastic: transmittance table outside mi_scene_desc::bsdf_tables";
     }
-    const int off[7][3] = { { 0, -1, -1 }, { 1, 4, -1 }, { 2, 5, 8 }, { 2, 5, 8 }, { 4, 7, -1 }, { 4, 7, -1 }, { 6, 9, -1 } };   // RGB layout of params[]
+    const int off[BSDF_TYPE_COUNT][3] = { { 0, -1, -1 }, { 1, 4, -1 }, { 2, 5, 8 }, { 2, 5, 8 }, { 4, 7, -1 }, { 4, 7, -1 }, { 6, 9, -1 },
+                                          { 1, 4, -1 }, { -1, -1, -1 }, { 0, -1, -1 }, { 0, -1, -1 } };   // RGB layout of params[]
     for (int k = 0; k < 3; ++k) {
         *bad = k;
         const bool used = k < (int) bsdf_tex_slots(b.type);
@@ -77,6 +83,8 @@ inline const char *bsdf_record_from_abi(const mi_bsdf &b, uint32_t bitmap_count,
 #if MIW_SPECTRAL
         if (!used) continue;
         if (b.tex[k].type == MI_TEX_RGB || b.tex[k].type > MI_TEX_SRGB_D65) return "the scalar_spectral library needs a spectral texture record";
+        if ((b.type == BSDF_TYPE_MASK || b.type == BSDF_TYPE_BLEND) && b.tex[k].type != MI_TEX_UNIFORM)
+            return "an opacity / weight is a uniform value or a one-channel bitmap";    // Texture::eval_1
         std::memcpy(&r.tex[k], &b.tex[k], sizeof(TexRec));
 #else
         r.tex[k].type = TEX_RGB;
@@ -88,6 +96,36 @@ inline const char *bsdf_record_from_abi(const mi_bsdf &b, uint32_t bitmap_count,
     return nullptr;
 }
 
+// The nesting rules of a table built by bsdf_record_from_abi (bsdf.h: one chain [mask ->] [blendbsdf ->] leaf per record, so that
+// bsdf_side needs no recursion; twosided.cpp:62-92 for the adapter). `bitmaps` = the scene's table, to refuse what eval_1 of the
+// variant refuses (bitmap.cpp:288-293). nullptr, or what is wrong with record i.
+inline const char *bsdf_chain_check(const std::vector<BsdfRec> &t, uint32_t i, const mi_bitmap *bitmaps) {
+    const BsdfRec &r = t[i];
+    const uint32_t n = (uint32_t) t.size();
+    auto wrapper = [](const BsdfRec &x) { return x.type == BSDF_TYPE_MASK || x.type == BSDF_TYPE_BLEND; };
+    if (wrapper(r)) {
+        if (r.back >= n) return r.type == BSDF_TYPE_MASK ? "mask: nested record out of range" : "blendbsdf: first child out of range";
+        if (r.type == BSDF_TYPE_MASK && t[r.back].type == BSDF_TYPE_MASK) return "mask: a mask cannot be nested in a mask";
+        if (r.type == BSDF_TYPE_BLEND) {
+            if ((uint32_t) r.p[3] >= n) return "blendbsdf: second child out of range";
+            if (wrapper(t[r.back]) || wrapper(t[(uint32_t) r.p[3]])) return "blendbsdf: its children must be leaf records (no mask or blendbsdf under a blendbsdf)";
+        }
+        if (r.tex[0].type == TEX_BITMAP && bitmaps) {
+            const mi_bitmap &bm = bitmaps[(uint32_t) r.tex[0].v[0]];
+#if MIW_SPECTRAL
+            if (bm.channels != 1) return "the opacity / weight bitmap was converted to colour spectra: eval_1 needs one channel";
+#endif
+            (void) bm;
+        }
+    }
+    if (r.flags & BSDF_REC_TWOSIDED) {
+        if (r.back >= n) return "back-side record out of range";
+        if (wrapper(t[r.back])) return "twosided: a mask / blendbsdf cannot be nested in twosided (wrap its children instead)";
+        if ((bsdf_flags(r) | bsdf_flags(t[r.back])) & (BSDF_Transmission | BSDF_Null)) return "only materials without a transmission component can be nested";
+    }
+    return nullptr;
+}
+inline bool bsdf_is_nested(const BsdfRec &r) { return r.type >= BSDF_TYPE_THINDIELECTRIC && r.type <= BSDF_TYPE_BLEND; }   // -> the MATS_NESTED kernels
 // true when a record of the table reads a bitmap
 // true when the record needs an "extended" kernel (plugins the plain kernels compile out)
 inline bool bsdf_is_extended(const BsdfRec &r) { return r.type == BSDF_TYPE_ROUGHPLASTIC; }

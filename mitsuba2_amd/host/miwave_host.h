@@ -308,11 +308,16 @@ public:
     // twosided adapter: the nested back-side BSDF (nullptr: not twosided; == this: same BSDF on both sides)
     const std::shared_ptr<BSDF> &back() const { return m_back; }
     bool twosided() const { return (m_rec.flags & MI_BSDF_FLAG_TWOSIDED) != 0; }
+    // mask: child(0) = the nested BSDF; blendbsdf: child(0), child(1); nullptr otherwise. Scene::build flattens them into
+    // the record table (mi_bsdf::back and params[3] become their indices).
+    const std::shared_ptr<BSDF> &child(int k) const { return m_child[k]; }
+    bool wrapper() const { return m_rec.type == MI_BSDF_MASK || m_rec.type == MI_BSDF_BLEND; }
 protected:
     // m_rec.tex[slot] = props.texture_record(...) and remember the bitmap, if the property holds one
     void bind_texture(int slot, const Properties &props, const std::string &name, float def, bool unbounded);
     mi_bsdf m_rec{};
     std::shared_ptr<BSDF> m_back;
+    std::shared_ptr<BSDF> m_child[2];
     std::shared_ptr<BitmapTexture> m_bitmaps[3];
     std::vector<float> m_table;
 };
@@ -330,6 +335,19 @@ class RoughPlastic final : public BSDF { public: explicit RoughPlastic(const Pro
 void gauss_legendre(int n, std::vector<float> &nodes, std::vector<float> &weights);
 // twosided.cpp:62-92: wraps one nested BRDF (both sides) or two (front, back); nested BSDFs must not transmit
 class TwoSidedBRDF final : public BSDF { public: explicit TwoSidedBRDF(std::shared_ptr<BSDF> front, std::shared_ptr<BSDF> back = nullptr); };
+class ThinDielectric final : public BSDF { public: explicit ThinDielectric(const Properties &props); };     // thindielectric.cpp:78-99
+class Null final : public BSDF { public: explicit Null(const Properties &props); };                          // null.cpp:33-40
+// mask.cpp:68-91: `opacity` (default 0.5) in front of one nested BSDF
+class Mask final : public BSDF { public: Mask(const Properties &props, const std::vector<std::shared_ptr<BSDF>> &nested); };
+// blendbsdf.cpp:59-81: `weight` (required) between two nested BSDFs
+class BlendBSDF final : public BSDF {
+public:
+    BlendBSDF(const Properties &props, const std::vector<std::shared_ptr<BSDF>> &nested);
+    BlendBSDF(const BlendBSDF &weight_of, std::shared_ptr<BSDF> child0, std::shared_ptr<BSDF> child1);     // the same weight over other children
+};
+// <bsdf type="twosided">: TwoSidedBRDF, except that twosided(blendbsdf(a, b)) with one nested material becomes
+// blendbsdf(twosided(a), twosided(b)) — the record table has no wrapper under the adapter (DESIGN.md says why the bits agree)
+std::shared_ptr<BSDF> make_twosided(std::shared_ptr<BSDF> front, std::shared_ptr<BSDF> back);
 float fresnel_diffuse_reflectance(float eta);                                                                 // fresnel.h:327-361
 float lookup_ior(const Properties &props, const std::string &name, const std::string &def);                   // include/mitsuba/render/ior.h
 

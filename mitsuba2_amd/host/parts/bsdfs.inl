@@ -28,21 +28,45 @@ static const miw::BsdfRec &as_rec(const mi_bsdf &b) { return *reinterpret_cast<c
 uint32_t BSDF::flags() const {
     uint32_t f = miw::bsdf_flags(as_rec(m_rec));
     if (m_back) f |= miw::bsdf_flags(as_rec(m_back->record()));    // twosided.cpp:76-86
+    for (int k = 0; k < 2; ++k) if (m_child[k]) f |= m_child[k]->flags();   // mask.cpp:90, blendbsdf.cpp:80
     return f;
 }
 // the plugin as the integrator sees it: a two-record table {front, back} for the twosided adapter
-namespace { struct SideTable { miw::BsdfRec t[2]; std::vector<float> tables; };
-SideTable side_table(const mi_bsdf &rec, const std::shared_ptr<BSDF> &back, const std::vector<float> &table) {
-    SideTable s; s.t[0] = as_rec(rec); s.t[1] = back ? as_rec(back->record()) : as_rec(rec);
-    s.t[0].back = 1; s.t[1].flags &= ~(uint32_t) MI_BSDF_FLAG_TWOSIDED;
-    s.tables = table;                                          // front's table at offset 0, the back side's behind it
-    if (s.t[0].type == miw::BSDF_TYPE_ROUGHPLASTIC) s.t[0].p[5] = 0.f;
-    if (s.t[1].type == miw::BSDF_TYPE_ROUGHPLASTIC) {
-        const std::vector<float> &bt = back ? back->table() : table;
-        s.t[1].p[5] = (float) s.tables.size();
-        s.tables.insert(s.tables.end(), bt.begin(), bt.end());
+// (a wrapper's children follow it, each with its own back side: the table Scene::build makes for one shape)
+namespace { struct SideTable { std::vector<miw::BsdfRec> t; std::vector<float> tables; };
+uint32_t side_table_push(SideTable &s, const mi_bsdf &rec, const std::shared_ptr<BSDF> &back, const std::shared_ptr<BSDF> *child, const std::vector<float> &table) {
+    const uint32_t self = (uint32_t) s.t.size();
+    auto push = [&s](miw::BsdfRec r, const std::vector<float> &tb) {
+        if (r.type == miw::BSDF_TYPE_ROUGHPLASTIC) { r.p[5] = (float) s.tables.size(); s.tables.insert(s.tables.end(), tb.begin(), tb.end()); }
+        s.t.push_back(r);
+    };
+    push(as_rec(rec), table);
+    if (rec.type == MI_BSDF_MASK || rec.type == MI_BSDF_BLEND) {
+        const uint32_t c0 = side_table_push(s, child[0]->record(), child[0]->back(), &child[0]->child(0), child[0]->table());
+        s.t[self].back = c0;
+        if (rec.type == MI_BSDF_BLEND) s.t[self].p[3] = (float) side_table_push(s, child[1]->record(), child[1]->back(), &child[1]->child(0), child[1]->table());
+        return self;
     }
+    miw::BsdfRec b = back ? as_rec(back->record()) : as_rec(rec);
+    b.flags &= ~(uint32_t) MI_BSDF_FLAG_TWOSIDED;
+    s.t[self].back = (uint32_t) s.t.size();
+    push(b, back ? back->table() : table);
+    return self;
+}
+SideTable side_table(const mi_bsdf &rec, const std::shared_ptr<BSDF> &back, const std::shared_ptr<BSDF> *child, const std::vector<float> &table) {
+    SideTable s;
+    side_table_push(s, rec, back, child, table);
     return s;
+}
+// these helpers carry no surface interaction: a bitmap stands in with its mean colour (Properties::texture_record), which is fine for a
+// leaf's reflectance in a test and wrong for a decision — a wrapper whose opacity / weight is a bitmap is refused
+void require_constant_wrappers(const BSDF &b) {
+    const uint32_t type = b.record().type;
+    if (type != MI_BSDF_MASK && type != MI_BSDF_BLEND) return;
+    if (b.bitmap(0))
+        Throw(std::string("BSDF::sample / eval / pdf on the host: the ") + (type == MI_BSDF_MASK ? "opacity of a mask" : "weight of a blendbsdf") +
+              " is a bitmap texture, which needs the texture coordinates of a hit (render the scene instead)");
+    for (int k = 0; k < 2; ++k) if (b.child(k)) require_constant_wrappers(*b.child(k));
 }
 miw::TexCtx host_ctx(const SideTable &s) { return miw::TexCtx(miw::Wavelengths(), miw::v2(0.f, 0.f), nullptr, s.tables.empty() ? nullptr : s.tables.data()); } }
 #if MIW_SPECTRAL
@@ -52,17 +76,19 @@ std::pair<BSDFSample3f, Color3f> BSDF::sample(const Vector3f &, float, const std
 Color3f BSDF::eval(const Vector3f &, const Vector3f &) const { Throw("BSDF::eval on the host is a scalar_rgb test helper"); }
 #else
 std::pair<BSDFSample3f, Color3f> BSDF::sample(const Vector3f &wi, float s1, const std::array<float, 2> &s2) const {
+    require_constant_wrappers(*this);
     miw::BSDFSample bs;
-    const SideTable tab = side_table(m_rec, m_back, m_table);
+    const SideTable tab = side_table(m_rec, m_back, m_child, m_table);
     const miw::V3 wi_ = miw::v3(wi[0], wi[1], wi[2]);
-    miw::V3 w = miw::bsdf_side_sample(miw::bsdf_side(tab.t, 0, wi_), wi_, s1, miw::v2(s2[0], s2[1]), bs, host_ctx(tab));
+    miw::V3 w = miw::bsdf_side_sample(miw::bsdf_side(tab.t.data(), 0, wi_), wi_, s1, miw::v2(s2[0], s2[1]), bs, host_ctx(tab));
     BSDFSample3f o; o.wo = { bs.wo.x, bs.wo.y, bs.wo.z }; o.pdf = bs.pdf; o.eta = bs.eta; o.sampled_type = bs.sampled_type;
     return { o, Color3f{ w.x, w.y, w.z } };
 }
 Color3f BSDF::eval(const Vector3f &wi, const Vector3f &wo) const {
-    const SideTable tab = side_table(m_rec, m_back, m_table);
+    require_constant_wrappers(*this);
+    const SideTable tab = side_table(m_rec, m_back, m_child, m_table);
     const miw::V3 wi_ = miw::v3(wi[0], wi[1], wi[2]);
-    miw::V3 v = miw::bsdf_side_eval(miw::bsdf_side(tab.t, 0, wi_), wi_, miw::v3(wo[0], wo[1], wo[2]), host_ctx(tab));
+    miw::V3 v = miw::bsdf_side_eval(miw::bsdf_side(tab.t.data(), 0, wi_), wi_, miw::v3(wo[0], wo[1], wo[2]), host_ctx(tab));
     return { v.x, v.y, v.z };
 }
 #endif
@@ -78,9 +104,10 @@ std::pair<BSDFSample3f, Color3f> BSDF::sample(const BSDFContext &ctx, const Surf
 Color3f BSDF::eval(const BSDFContext &ctx, const SurfaceInteraction3f &si, const Vector3f &wo) const { require_full_context(ctx); return eval(si.wi, wo); }
 float BSDF::pdf(const BSDFContext &ctx, const SurfaceInteraction3f &si, const Vector3f &wo) const { require_full_context(ctx); return pdf(si.wi, wo); }
 float BSDF::pdf(const Vector3f &wi, const Vector3f &wo) const {
-    const SideTable tab = side_table(m_rec, m_back, m_table);
+    require_constant_wrappers(*this);
+    const SideTable tab = side_table(m_rec, m_back, m_child, m_table);
     const miw::V3 wi_ = miw::v3(wi[0], wi[1], wi[2]);
-    return miw::bsdf_side_pdf(miw::bsdf_side(tab.t, 0, wi_), wi_, miw::v3(wo[0], wo[1], wo[2]), host_ctx(tab));
+    return miw::bsdf_side_pdf(miw::bsdf_side(tab.t.data(), 0, wi_), wi_, miw::v3(wo[0], wo[1], wo[2]), host_ctx(tab));
 }
 
 void BSDF::bind_texture(int slot, const Properties &props, const std::string &name, float def, bool unbounded) {
@@ -402,11 +429,63 @@ RoughPlastic::RoughPlastic(const Properties &props) {
     bind_texture(0, props, "diffuse_reflectance", .5f, false);
     bind_texture(1, props, "specular_reflectance", 1.f, false);
 }
+ThinDielectric::ThinDielectric(const Properties &props) {
+    float int_ior = lookup_ior(props, "int_ior", "bk7"), ext_ior = lookup_ior(props, "ext_ior", "air");
+    if (int_ior < 0.f || ext_ior < 0.f) Throw("The interior and exterior indices of refraction must be positive!");
+    Color3f sr = props.texture("specular_reflectance", 1.f), stt = props.texture("specular_transmittance", 1.f);
+    check_reflectance(sr, "specular_reflectance"); check_reflectance(stt, "specular_transmittance");
+    m_rec.type = MI_BSDF_THINDIELECTRIC; m_rec.flags = 0;
+    m_rec.params[0] = int_ior / ext_ior;
+    for (int i = 0; i < 3; ++i) { m_rec.params[1 + i] = sr[i]; m_rec.params[4 + i] = stt[i]; }
+    bind_texture(0, props, "specular_reflectance", 1.f, false);
+    bind_texture(1, props, "specular_transmittance", 1.f, false);
+}
+Null::Null(const Properties &) { m_rec.type = MI_BSDF_NULL; m_rec.flags = 0; }
+// Texture::eval_1 needs a scalar: a <float> / <spectrum value="v"/> or a bitmap (uniform.cpp:42-45, bitmap.cpp:285-302)
+static void bind_scalar_texture(mi_bsdf &rec, const Properties &props, const std::string &name, const char *plugin) {
+    if (!props.bitmap(name)) {
+        const Color3f c = props.texture(name);
+        if (c[0] != c[1] || c[0] != c[2]) Throw(std::string(plugin) + ": \"" + name + "\" must be a scalar value or a bitmap texture");
+    }
+    const Color3f v = props.texture(name);
+    for (int i = 0; i < 3; ++i) rec.params[i] = v[i];
+}
+Mask::Mask(const Properties &props, const std::vector<std::shared_ptr<BSDF>> &nested) {
+    if (nested.size() > 1) Throw("Cannot specify more than one child BSDF");                   // mask.cpp:75-76
+    if (nested.empty() || !nested[0]) Throw("Child BSDF not specified");                        // :81-82
+    if (nested[0]->record().type == MI_BSDF_MASK) Throw("mask: a mask nested in a mask is not supported");
+    Properties p = props;
+    if (!p.has_property("opacity")) p.set_float("opacity", .5f);                                // :70
+    m_rec.type = MI_BSDF_MASK; m_rec.flags = 0;
+    bind_scalar_texture(m_rec, p, "opacity", "mask");
+    bind_texture(0, p, "opacity", .5f, true);
+    m_child[0] = nested[0];
+}
+BlendBSDF::BlendBSDF(const Properties &props, const std::vector<std::shared_ptr<BSDF>> &nested) {
+    if (nested.size() > 2) Throw("BlendBSDF: Cannot specify more than two child BSDFs");       // blendbsdf.cpp:64-65
+    if (!props.has_property("weight")) Throw("Property \"weight\" has not been specified!");     // :71
+    if (nested.size() != 2 || !nested[0] || !nested[1]) Throw("BlendBSDF: Two child BSDFs must be specified!");   // :72-73
+    for (auto &c : nested) if (c->wrapper()) Throw("blendbsdf: a mask or blendbsdf nested in a blendbsdf is not supported");
+    m_rec.type = MI_BSDF_BLEND; m_rec.flags = 0;
+    bind_scalar_texture(m_rec, props, "weight", "blendbsdf");
+    bind_texture(0, props, "weight", 0.f, true);
+    m_child[0] = nested[0]; m_child[1] = nested[1];
+}
+BlendBSDF::BlendBSDF(const BlendBSDF &weight_of, std::shared_ptr<BSDF> child0, std::shared_ptr<BSDF> child1) {
+    m_rec = weight_of.m_rec; m_bitmaps[0] = weight_of.m_bitmaps[0];
+    m_child[0] = std::move(child0); m_child[1] = std::move(child1);
+}
+std::shared_ptr<BSDF> make_twosided(std::shared_ptr<BSDF> front, std::shared_ptr<BSDF> back) {
+    if (front && !back && front->record().type == MI_BSDF_BLEND)
+        return std::make_shared<BlendBSDF>(static_cast<const BlendBSDF &>(*front), make_twosided(front->child(0), nullptr), make_twosided(front->child(1), nullptr));
+    return std::make_shared<TwoSidedBRDF>(front, back);
+}
 TwoSidedBRDF::TwoSidedBRDF(std::shared_ptr<BSDF> front, std::shared_ptr<BSDF> back) {
     if (!front) Throw("A nested one-sided material is required!");
     if (front->twosided() || (back && back->twosided())) Throw("twosided: nested twosided materials are not supported");
+    if (front->wrapper() || (back && back->wrapper())) Throw("twosided: a mask or blendbsdf can only be nested as twosided(blendbsdf(a, b)) with one nested material");
     if (!back) back = front;
-    if ((front->flags() | back->flags()) & miw::BSDF_Transmission)
+    if ((front->flags() | back->flags()) & (miw::BSDF_Transmission | miw::BSDF_Null))
         Throw("Only materials without a transmission component can be nested!");
     m_rec = front->record();
     m_rec.flags |= MI_BSDF_FLAG_TWOSIDED;

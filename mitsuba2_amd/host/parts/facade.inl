@@ -52,6 +52,8 @@ void *mih_bsdf_create(void *props) {
         else if (p.plugin_name() == "plastic") b = std::make_shared<SmoothPlastic>(p);
         else if (p.plugin_name() == "roughdielectric") b = std::make_shared<RoughDielectric>(p);
         else if (p.plugin_name() == "roughplastic") b = std::make_shared<RoughPlastic>(p);
+        else if (p.plugin_name() == "thindielectric") b = std::make_shared<ThinDielectric>(p);
+        else if (p.plugin_name() == "null") b = std::make_shared<Null>(p);
         else throw std::runtime_error("Plugin \"" + p.plugin_name() + "\" not found!");
         return new Box<BSDF>{ b }; MIH_CATCH(nullptr)
 }
@@ -59,7 +61,19 @@ void *mih_bsdf_create(void *props) {
 void *mih_bsdf_create_twosided(void *front, void *back) {
     MIH_TRY
         std::shared_ptr<BSDF> f = front ? ((Box<BSDF> *) front)->p : nullptr, b = back ? ((Box<BSDF> *) back)->p : nullptr;
-        return new Box<BSDF>{ std::make_shared<TwoSidedBRDF>(f, b) }; MIH_CATCH(nullptr)
+        return new Box<BSDF>{ make_twosided(f, b) }; MIH_CATCH(nullptr)
+}
+// <bsdf type="mask"> / <bsdf type="blendbsdf">: `props` holds opacity / weight, `children` the nested BSDF handles in order
+void *mih_bsdf_create_nested(void *props, void *const *children, uint32_t count) {
+    MIH_TRY
+        const Properties &p = *(Properties *) props;
+        std::vector<std::shared_ptr<BSDF>> nested;
+        for (uint32_t i = 0; i < count; ++i) nested.push_back(children[i] ? ((Box<BSDF> *) children[i])->p : nullptr);
+        std::shared_ptr<BSDF> b;
+        if (p.plugin_name() == "mask") b = std::make_shared<Mask>(p, nested);
+        else if (p.plugin_name() == "blendbsdf") b = std::make_shared<BlendBSDF>(p, nested);
+        else throw std::runtime_error("Plugin \"" + p.plugin_name() + "\" takes no nested BSDFs");
+        return new Box<BSDF>{ b }; MIH_CATCH(nullptr)
 }
 float mih_fresnel_diffuse_reflectance(float eta) { return fresnel_diffuse_reflectance(eta); }
 void mih_bsdf_destroy(void *b) { delete (Box<BSDF> *) b; }

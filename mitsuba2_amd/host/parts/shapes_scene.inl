@@ -392,6 +392,26 @@ static void flatten(const std::vector<std::shared_ptr<Mesh>> &shapes, std::vecto
         }
         brecs.push_back(r);
     };
+    // the record of a BSDF, pushed at its first use; a twosided record is followed by its back side's, a wrapper by its children's
+    std::function<uint32_t(const BSDF *)> index_of = [&](const BSDF *b) -> uint32_t {
+        auto it = bsdf_index.find(b);
+        if (it != bsdf_index.end()) return it->second;
+        const uint32_t self = (uint32_t) brecs.size();
+        bsdf_index.emplace(b, self);
+        push_record(b);
+        if (b->twosided()) {                                   // the back side's record follows (or is the front's own)
+            const BSDF *back = b->back().get();
+            bool same_bitmaps = true;
+            for (int k = 0; k < 3; ++k) same_bitmaps = same_bitmaps && back->bitmap(k) == b->bitmap(k);
+            if (same_bitmaps && miw_same_record(back->record(), b->record())) brecs[self].back = self;
+            else { const uint32_t j = index_of(back); brecs[self].back = j; }
+        } else if (b->wrapper()) {                             // mask: the nested record; blendbsdf: child 0, child 1 in params[3]
+            const uint32_t c0 = index_of(b->child(0).get());
+            brecs[self].back = c0;
+            if (b->child(1)) { const uint32_t c1 = index_of(b->child(1).get()); brecs[self].params[3] = (float) c1; }
+        }
+        return self;
+    };
     for (auto &m : shapes) {
         uint32_t vbase = (uint32_t) (pos.size() / 3), fbase = (uint32_t) (faces.size() / 3);
         pos.insert(pos.end(), m->vertex_positions_buffer().begin(), m->vertex_positions_buffer().end());
@@ -412,24 +432,7 @@ static void flatten(const std::vector<std::shared_ptr<Mesh>> &shapes, std::vecto
             b = std::make_shared<SmoothDiffuse>(p);
             m->set_bsdf(b);
         }
-        auto it = bsdf_index.find(b.get());
-        if (it == bsdf_index.end()) {
-            it = bsdf_index.emplace(b.get(), (uint32_t) brecs.size()).first;
-            push_record(b.get());
-            if (b->twosided()) {                                   // the back side's record follows (or is the front's own)
-                const uint32_t self = it->second;
-                const BSDF *back = b->back().get();
-                bool same_bitmaps = true;
-                for (int k = 0; k < 3; ++k) same_bitmaps = same_bitmaps && back->bitmap(k) == b->bitmap(k);
-                if (same_bitmaps && miw_same_record(back->record(), b->record())) brecs[self].back = self;
-                else {
-                    auto jt = bsdf_index.find(back);
-                    if (jt == bsdf_index.end()) { jt = bsdf_index.emplace(back, (uint32_t) brecs.size()).first; push_record(back); }
-                    brecs[self].back = jt->second;
-                }
-            }
-        }
-        s.bsdf = it->second;
+        s.bsdf = index_of(b.get());
         s.emitter = -1;
         if (m->emitter()) {
             s.emitter = (int32_t) erecs.size();

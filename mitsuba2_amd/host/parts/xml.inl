@@ -166,6 +166,8 @@ std::shared_ptr<BSDF> make_bsdf(const Properties &p) {
     if (t == "plastic") return std::make_shared<SmoothPlastic>(p);
     if (t == "roughdielectric") return std::make_shared<RoughDielectric>(p);
     if (t == "roughplastic") return std::make_shared<RoughPlastic>(p);
+    if (t == "thindielectric") return std::make_shared<ThinDielectric>(p);
+    if (t == "null") return std::make_shared<Null>(p);
     Throw("Plugin \"" + t + "\" not found!");
 }
 std::string resolve(const XmlCtx &cx, const std::string &f) { return (!f.empty() && f[0] == '/') ? f : cx.base_dir + "/" + f; }
@@ -194,7 +196,24 @@ std::shared_ptr<BSDF> parse_bsdf(XmlCtx &cx, const XmlNode &n) {
             } else Throw("Error while loading XML: unexpected <" + c->tag + "> inside <bsdf>");
         }
         if (nested.size() > 2) Throw("At most two nested BSDFs can be specified!");
-        b = std::make_shared<TwoSidedBRDF>(nested.empty() ? nullptr : nested[0], nested.size() == 2 ? nested[1] : nullptr);
+        b = make_twosided(nested.empty() ? nullptr : nested[0], nested.size() == 2 ? nested[1] : nullptr);
+    } else if (p.plugin_name() == "mask" || p.plugin_name() == "blendbsdf") {   // nested <bsdf> / <ref id> children + an opacity / weight texture
+        std::vector<std::shared_ptr<BSDF>> nested;
+        for (const XmlNode *c : objs) {
+            if (c->tag == "bsdf") nested.push_back(parse_bsdf(cx, *c));
+            else if (c->tag == "texture") p.set_texture(cx.get(*c, "name"), parse_texture(cx, *c));
+            else if (c->tag == "ref" && c->attr.count("name")) {
+                auto it = cx.textures.find(cx.get(*c, "id"));
+                if (it == cx.textures.end()) Throw("Error while loading XML: reference to unknown object \"" + cx.get(*c, "id") + "\"!");
+                p.set_texture(cx.get(*c, "name"), it->second);
+            } else if (c->tag == "ref") {
+                auto it = cx.bsdfs.find(cx.get(*c, "id"));
+                if (it == cx.bsdfs.end()) Throw("Error while loading XML: reference to unknown object \"" + cx.get(*c, "id") + "\"");
+                nested.push_back(it->second);
+            } else Throw("Error while loading XML: unexpected <" + c->tag + "> inside <bsdf>");
+        }
+        if (p.plugin_name() == "mask") b = std::make_shared<Mask>(p, nested);
+        else b = std::make_shared<BlendBSDF>(p, nested);
     } else {
         for (const XmlNode *c : objs) {                        // <texture type="bitmap" name=...> / <ref id=... name=...>
             if (c->tag == "texture") p.set_texture(cx.get(*c, "name"), parse_texture(cx, *c));

@@ -187,6 +187,84 @@ def plugin_box(width, height, spp, seed=0, device=0, rfilter="gaussian", **film_
     return scene, cornell_sensor(width, height, spp, seed, rfilter, **film_kw)
 
 
+
+def _panel(name, corners, bsdf):
+    """one quad with texture coordinates (0,0) (1,0) (1,1) (0,1) at its corners, wound as given"""
+    v = np.asarray(corners, np.float32)
+    uv = np.array([(0, 0), (1, 0), (1, 1), (0, 1)], np.float32)
+    return api.Mesh(name, v, np.array([(0, 1, 2), (0, 2, 3)], np.uint32), bsdf=bsdf, texcoords=uv)
+
+
+def cutout_opacity():
+    """8 x 8 opacity of the cut-out panel: a hole pattern of exact 0 and exact 1 with a ramp of values in between"""
+    a = np.zeros((8, 8), np.float32)
+    a[1:7, 1:7] = 1.0
+    a[3:5, 3:5] = 0.0
+    a[:, 0] = np.linspace(0.125, 0.875, 8, dtype=np.float32)
+    a[7, :] = 0.5
+    return a
+
+
+def cutout_weight():
+    """8 x 8 blend weight: a checkerboard of exact 0 and exact 1 with one row of 0.25 and one of 0.75"""
+    y, x = np.mgrid[0:8, 0:8]
+    a = ((x + y) & 1).astype(np.float32)
+    a[2, :] = 0.25
+    a[5, :] = 0.75
+    return a
+
+
+def cutout_box_meshes(wrappers=True, proxy=True, ball_level=None):
+    """The Cornell box plus the nested-BSDF plugins: a thindielectric pane under the light, a null rectangle in front of the
+    camera (every camera ray crosses it), a mask(twosided(diffuse)) cut-out panel with an 8 x 8 nearest-filtered opacity bitmap,
+    a blendbsdf(diffuse, roughconductor) panel of constant weight 0.3, one with a bitmap weight, and mask(blendbsdf(plastic,
+    conductor)) — the longest chain the record table takes. 24 triangles: a packet scene. `wrappers` = False puts the first
+    child in place of every wrapper (same geometry, plain leaves); `proxy` = False leaves the null rectangle out (behind it the
+    direct integrator sees emitters only: the Null lobe is its one bounce). `ball_level` adds an icosphere of 20 * 4**level
+    triangles with a blendbsdf(roughconductor, diffuse) material on the floor: past 64 triangles the scene walks a tree (the phase
+    machine by default)."""
+    white = api.BSDF("diffuse", reflectance=WHITE)
+    red = api.BSDF("diffuse", reflectance=RED)
+    green = api.BSDF("diffuse", reflectance=GREEN)
+    meshes = []
+    for name, bsdf in (("floor", white), ("ceiling", white), ("back", white), ("right", green), ("left", red)):
+        v, f = _quad(_CBOX[name], inward_point=_ROOM_CENTER)
+        meshes.append(api.Mesh(name, v, f, bsdf=bsdf))
+    v, f = _quad(_CBOX["light"], inward_point=_ROOM_CENTER)
+    meshes.append(api.Mesh("light", v, f, emitter=api.AreaLight(LIGHT_RADIANCE)))
+    nearest = dict(filter_type="nearest", wrap_mode="clamp")
+    # (smaller than the light: a shadow ray that meets the pane is occluded — the reference's ray_test knows no Null lobe)
+    pane = api.BSDF("thindielectric", int_ior=1.5046, ext_ior=1.000277)
+    meshes.append(_panel("pane", [(233, 480, 240), (323, 480, 240), (323, 480, 320), (233, 480, 320)], pane))
+    if proxy:
+        meshes.append(_panel("proxy", [(-200, -200, -40), (760, -200, -40), (760, 750, -40), (-200, 750, -40)], api.BSDF("null")))
+    leaf = api.TwoSided(api.BSDF("diffuse", reflectance=(0.2, 0.7, 0.3)))
+    cut = api.Mask(leaf, opacity=api.BitmapTexture(cutout_opacity(), **nearest)) if wrappers else leaf
+    meshes.append(_panel("cutout", [(60, 0, 330), (190, 0, 250), (190, 260, 250), (60, 260, 330)], cut))
+    paint = api.BSDF("diffuse", reflectance=(0.7, 0.25, 0.1))
+    metal = api.BSDF("roughconductor", distribution="ggx", alpha=0.2, eta=(0.2, 0.92, 1.1), k=(3.9, 2.45, 2.14))
+    dirty = api.BlendBSDF(paint, metal, weight=0.3) if wrappers else paint
+    meshes.append(_panel("dirty", [(330, 0, 200), (215, 0, 200), (215, 200, 200), (330, 200, 200)], dirty))
+    paint2 = api.BSDF("diffuse", reflectance=(0.15, 0.3, 0.75))
+    metal2 = api.BSDF("roughconductor", distribution="ggx", alpha=0.3, eta=(1.66, 0.88, 0.52), k=(9.2, 6.3, 4.8))
+    checker = api.BlendBSDF(paint2, metal2, weight=api.BitmapTexture(cutout_weight(), **nearest)) if wrappers else paint2
+    meshes.append(_panel("checker", [(490, 0, 400), (350, 0, 330), (350, 300, 330), (490, 300, 400)], checker))
+    plastic = api.BSDF("plastic", diffuse_reflectance=(0.6, 0.6, 0.2), int_ior=1.49, ext_ior=1.000277)
+    mirror = api.BSDF("conductor", eta=(0.2, 0.92, 1.1), k=(3.9, 2.45, 2.14))
+    chain = api.Mask(api.BlendBSDF(plastic, mirror, weight=0.6), opacity=0.7) if wrappers else plastic
+    if ball_level is not None:
+        gold = api.BSDF("roughconductor", distribution="ggx", alpha=0.15, eta=(0.2, 0.92, 1.1), k=(3.9, 2.45, 2.14))
+        v, f, n = icosphere((120.0, 60.0, 120.0), 60.0, ball_level)
+        meshes.append(api.Mesh("ball", v, f, normals=n, bsdf=api.BlendBSDF(gold, paint2, weight=0.5) if wrappers else gold))
+    meshes.append(_panel("chain", [(520, 0, 170), (380, 0, 120), (380, 150, 120), (520, 150, 170)], chain))
+    return meshes
+
+
+def cutout_box(width, height, spp, seed=0, device=0, rfilter="gaussian", wrappers=True, proxy=True, ball_level=None, bvh_quality=0, **film_kw):
+    """-> (scene, sensor): the nested-BSDF test scene (cutout_box_meshes). bvh_quality=MI_BVH_FORCE_TREE takes the tree route."""
+    scene = api.Scene(cutout_box_meshes(wrappers, proxy, ball_level)).build(device, bvh_quality)
+    return scene, cornell_sensor(width, height, spp, seed, rfilter, **film_kw)
+
 def _rect(name, corners, inward_point, **kw):
     """api.Mesh.rectangle over the parallelogram corners[0] + s * (corners[1] - corners[0]) + t * (corners[3] - corners[0]),
     normal towards `inward_point`"""
