@@ -166,6 +166,26 @@ typedef struct {
     float to_world[16], to_object[16];
 } mi_sphere;
 
+/* The shapeless emitters: src/emitters/point.cpp, spot.cpp, directional.cpp, constant.cpp. One record per emitter, in
+ * mi_scene_desc::lights. Matrices 4x4 column-major. */
+enum { MI_LIGHT_POINT = 0, MI_LIGHT_SPOT = 1, MI_LIGHT_DIRECTIONAL = 2, MI_LIGHT_CONSTANT = 3 };
+typedef struct {
+    uint32_t type;                         /* MI_LIGHT_*                                                                  */
+    uint32_t emitter_index;                /* position among the scene's emitters (Scene::m_emitters order), as
+                                              mi_envmap::emitter_index: area emitters and the envmap at or after it shift up.
+                                              The indices of lights and envmap are distinct and leave no gap in 0 .. count-1  */
+    float value[3];                        /* scalar_rgb: intensity (point, spot), irradiance (directional), radiance (constant) */
+    mi_texture value_tex;                  /* scalar_spectral: MI_TEX_SRGB_D65 / MI_TEX_D65 / MI_TEX_UNIFORM, as mi_emitter::radiance_tex.
+                                              Spot: a spatially varying `texture` child (MI_TEX_BITMAP here) is refused          */
+    float position[3];                     /* point, spot: to_world.translation()                                          */
+    float direction[3];                    /* directional: to_world.transform_affine((0, 0, 1)), unit length               */
+    float to_world[16], to_object[16];     /* spot: emitter-to-world and its inverse                                       */
+    float cutoff_angle, beam_width;        /* spot, radians (spot.cpp:88-91)                                               */
+    float cos_cutoff_angle, cos_beam_width, uv_factor, inv_transition_width;   /* spot: as the constructor derives them, :92-96 */
+    float bsphere_center[3], bsphere_radius;   /* directional, constant: scene->bbox().bounding_sphere(); the library applies
+                                              the set_scene enlargement (max(RayEpsilon, r (1 + RayEpsilon))) itself        */
+} mi_light;
+
 typedef struct {
     const float    *vertex_positions;  /* 3 * vertex_count                               */
     const float    *vertex_normals;    /* 3 * vertex_count, or NULL                      */
@@ -187,6 +207,9 @@ typedef struct {
     /* float tables plugins precompute in their constructors (roughplastic's eval_transmittance over
      * mu = i / 63, microfacet.h:504-552): one buffer, addressed by offsets stored in mi_bsdf::params */
     const float *bsdf_tables; uint32_t bsdf_table_floats;
+    /* point / spot / directional / constant emitters, or NULL / 0 (appended: the members above keep their offsets). At most one
+     * environment emitter per scene: a MI_LIGHT_CONSTANT record excludes `envmap` and a second constant record. */
+    const mi_light *lights; uint32_t light_count;
 } mi_scene_desc;
 enum { MI_ROUGH_TRANSMITTANCE_RES = 64 };
 

@@ -50,6 +50,13 @@ class mi_sphere(C.Structure):
                 ("to_world", C.c_float * 16), ("to_object", C.c_float * 16)]
 
 
+class mi_light(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("emitter_index", C.c_uint32), ("value", C.c_float * 3), ("value_tex", mi_texture),
+                ("position", C.c_float * 3), ("direction", C.c_float * 3), ("to_world", C.c_float * 16), ("to_object", C.c_float * 16),
+                ("cutoff_angle", C.c_float), ("beam_width", C.c_float), ("cos_cutoff_angle", C.c_float), ("cos_beam_width", C.c_float),
+                ("uv_factor", C.c_float), ("inv_transition_width", C.c_float), ("bsphere_center", C.c_float * 3), ("bsphere_radius", C.c_float)]
+
+
 class mi_bitmap(C.Structure):
     _fields_ = [("data", c_float_p), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32),
                 ("filter_type", C.c_uint32), ("wrap_mode", C.c_uint32), ("to_uv", C.c_float * 6)]
@@ -65,7 +72,8 @@ class mi_scene_desc(C.Structure):
                 ("rectangles", C.POINTER(mi_rectangle)), ("rectangle_count", C.c_uint32),
                 ("spheres", C.POINTER(mi_sphere)), ("sphere_count", C.c_uint32),
                 ("vertex_texcoords", c_float_p), ("bitmaps", C.POINTER(mi_bitmap)), ("bitmap_count", C.c_uint32),
-                ("bsdf_tables", c_float_p), ("bsdf_table_floats", C.c_uint32)]
+                ("bsdf_tables", c_float_p), ("bsdf_table_floats", C.c_uint32),
+                ("lights", C.POINTER(mi_light)), ("light_count", C.c_uint32)]
 
 
 class mi_rays_soa(C.Structure):
@@ -142,6 +150,7 @@ MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
 (MI_BSDF_DIFFUSE, MI_BSDF_DIELECTRIC, MI_BSDF_ROUGHCONDUCTOR, MI_BSDF_CONDUCTOR, MI_BSDF_PLASTIC, MI_BSDF_ROUGHDIELECTRIC,
  MI_BSDF_ROUGHPLASTIC, MI_BSDF_THINDIELECTRIC, MI_BSDF_NULL, MI_BSDF_MASK, MI_BSDF_BLEND) = range(11)
 MI_BSDF_FLAG_TWOSIDED = 0x100
+MI_LIGHT_POINT, MI_LIGHT_SPOT, MI_LIGHT_DIRECTIONAL, MI_LIGHT_CONSTANT = range(4)      # mi_light::type
 MI_BVH_FORCE_TREE, MI_BVH_NO_LEAF_FILTER, MI_BVH_RADIX_TREE = 0x10, 0x20, 0x40      # flags of mi_bvh_build's quality argument
 MI_OK, MI_ERR_INVALID, MI_ERR_DEVICE, MI_ERR_STATE, MI_ERR_CANCELLED = 0, -1, -2, -3, -4
 MI_EVAL = dict(PCG32=0, SINCOS=1, COSINE_HEMISPHERE=2, BSDF=3, FRESNEL=4, CAMERA_RAY=5, EMITTER_SAMPLE=6,
@@ -243,6 +252,8 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_mesh_set_bsdf": (None, [vp, vp]), "mih_mesh_set_emitter": (None, [vp, vp]),
         "mih_envmap_create": (vp, [vp, u32, u32, c_float_p]), "mih_envmap_destroy": (None, [vp]),
         "mih_scene_add_envmap": (i32, [vp, vp]),
+        "mih_light_create": (vp, [vp]), "mih_light_destroy": (None, [vp]), "mih_light_record": (None, [vp, C.POINTER(mi_light)]),
+        "mih_scene_add_light": (i32, [vp, vp]),
         "mih_load_xml": (i32, [cp, i32, cp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         "mih_scene_create": (vp, []), "mih_scene_destroy": (None, [vp]),
         "mih_scene_add_shape": (i32, [vp, vp]), "mih_scene_build": (i32, [vp, i32, i32]),

@@ -44,7 +44,7 @@ MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_ray_intersect(SceneView sc, SoaRa
     } else {                                                   // interaction.h:571-596 on an invalid pi: t = inf, wi = -ray.d
         r.t = MIW_INFINITY; st3(r.wi, -d);
         r.prim_index = r.shape_index = 0xffffffffu;
-        r.emitter_index = sc.env ? (int32_t) sc.env->emitter_index : -1;   // scene.h:248-249
+        r.emitter_index = miss_emitter<true>(sc);                  // scene.h:248-249
     }
     out[i] = r;
 }
@@ -65,7 +65,7 @@ MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_sample_emitter_direction(SceneVie
     const V3 ref = v3(ref_p[3 * i], ref_p[3 * i + 1], ref_p[3 * i + 2]);
     const V2 u = v2(sample[2 * i], sample[2 * i + 1]);
     DirectionSample ds;
-    Spec value = emitter < 0 ? sample_emitter_direction(sc, ref, u, ds, wl) : emitter_sample_direction(sc, (uint32_t) emitter, ref, u, ds, wl);
+    Spec value = emitter < 0 ? sample_emitter_direction<true, true>(sc, ref, u, ds, wl) : emitter_sample_direction<true, true>(sc, (uint32_t) emitter, ref, u, ds, wl);
     if (test_visibility && ds.pdf != 0.f) {                    // scene.cpp:203-207
         Hit h;
         if (trace_one<true>(sc, cfg, smem, ref, ds.d, spawn_mint(ref), ds.dist * (1.f - MIW_SHADOW_EPSILON), h)) value = spec(0.f);
@@ -85,7 +85,7 @@ MIW_KERNEL void k_pdf_emitter_direction(SceneView sc, int32_t emitter, const flo
     const uint32_t e = emitter < 0 ? (uint32_t) r.emitter_index : (uint32_t) emitter;
     float v = 0.f;
     if (e < sc.emitter_count)
-        v = emitter < 0 ? pdf_emitter_direction(sc, e, ld3(r.d), r.dist, ld3(r.n), ref) : emitter_pdf_direction(sc, e, ld3(r.d), r.dist, ld3(r.n), ref);
+        v = emitter < 0 ? pdf_emitter_direction<true, true>(sc, e, ld3(r.d), r.dist, ld3(r.n), ref) : emitter_pdf_direction<true, true>(sc, e, ld3(r.d), r.dist, ld3(r.n), ref);
     pdf[i] = v;
 }
 
@@ -103,6 +103,7 @@ MIW_KERNEL void k_emitter_eval(SceneView sc, const mi_surface_interaction *si, c
     if (r.emitter_index >= 0 && (uint32_t) r.emitter_index < sc.emitter_count) {
         const EmitterRec &e = sc.emitters[r.emitter_index];
         if (e.type == EMITTER_ENVMAP) { if (sc.env) value = env_eval_spec(*sc.env, -ld3(r.wi), wl); }   // envmap.cpp:137: v = to_local(-si.wi)
+        else if (e.type >= EMITTER_POINT) { if (sc.lights) value = light_eval(sc.lights[e.tri_first], wl); }   // constant.cpp:61-65; zero for the delta lights
         else value = emitter_eval(e, ld3(r.wi), wl);
     }
     const float *vf = reinterpret_cast<const float *>(&value);
@@ -152,7 +153,7 @@ MIW_KERNEL void k_eval(int op, RenderParams P, SceneView sc, const float *in, in
 #if MIW_SPECTRAL
             for (int k = 0; k < 4; ++k) wl.l[k] = a[5 + k];
 #endif
-            DirectionSample ds; Spec s = sample_emitter_direction(sc, v3(a[0], a[1], a[2]), v2(a[3], a[4]), ds, wl);
+            DirectionSample ds; Spec s = sample_emitter_direction<true, true>(sc, v3(a[0], a[1], a[2]), v2(a[3], a[4]), ds, wl);
             o[0] = ds.d.x; o[1] = ds.d.y; o[2] = ds.d.z; o[3] = ds.dist; o[4] = ds.pdf;
             o[5] = ds.p.x; o[6] = ds.p.y; o[7] = ds.p.z; o[8] = ds.n.x; o[9] = ds.n.y; o[10] = ds.n.z;
             const float *sf = reinterpret_cast<const float *>(&s);

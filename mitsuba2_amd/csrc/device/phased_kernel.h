@@ -109,7 +109,7 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves) void k_path_phased(RenderParams P
     stage_to_lds(sc, cfg, smem);
     const float *thr = stage_thresholds(smem, cfg, Q.log_rec ? Q.log_thr : nullptr);
 #if MIW_LDS_TABLES
-    stage_tables<false>(sc, cfg, smem);
+    stage_tables<false, mats_lights(Mats)>(sc, cfg, smem);
 #endif
     int32_t *stack = reinterpret_cast<int32_t *>(smem + cfg.stack16) + threadIdx.x;
     U2 *stack8 = reinterpret_cast<U2 *>(smem + cfg.stack16) + threadIdx.x;

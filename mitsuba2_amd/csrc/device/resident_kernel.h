@@ -277,7 +277,7 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
     stage_to_lds(sc, cfg, smem);
     const float *thr = stage_thresholds(smem, cfg, UseLog && Q.log_rec ? Q.log_thr : nullptr);
 #if MIW_LDS_TABLES
-    if constexpr (UseLog && Tiny != 0) stage_tables<true>(sc, cfg, smem);
+    if constexpr (UseLog && Tiny != 0) stage_tables<true, mats_lights(Mats)>(sc, cfg, smem);
 #endif
 #if defined(MIW_SECTION_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
     if ((threadIdx.x & 63u) == 0) { unsigned long long *b_ = miw_sec_buf(); for (int i = 0; i < 15; ++i) b_[i] = 0; b_[15] = __builtin_amdgcn_s_memtime(); }
@@ -315,11 +315,11 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
             if (T.side) {
                 TileAdd add; add.tile = tile; add.x0 = tile_x0; add.y0 = tile_y0; add.side = (int) T.side;
                 SplatXYSink<TileAdd> sink; sink.film = &P.film; sink.add = add;
-                st = pixel_render<Integ, Mats == MATS_NESTED ? MATS_NESTED : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
+                st = pixel_render<Integ, mats_nested(Mats) ? Mats : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
             } else {
                 FilmAdd add; add.accum = accum;
                 SplatSink<FilmAdd> sink; sink.film = &P.film; sink.add = add;
-                st = pixel_render<Integ, Mats == MATS_NESTED ? MATS_NESTED : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
+                st = pixel_render<Integ, mats_nested(Mats) ? Mats : MATS_ALL>(P, sc, pixel, st, sample_end, tr2, sink, &local);
             }
             Q.st[lane] = st;
         }

@@ -23,6 +23,7 @@ struct TraceLds {           // what a trace workgroup finds in its dynamic LDS
     uint32_t env_top_count, env_top_base, env_top_words;   // the environment warp's top levels behind the tables (envmap.h: EnvTop); 0: none
     uint32_t pool_claim_min; // k_path_pooled: a walk loop looks for new jobs only when this many lanes of a slot are empty
     uint32_t pool16, stat16; // k_path_pooled (pooled_kernel.h): uint4 offsets of the workgroup's walk-job records (5 x 16 B per lane) and of their status bytes
+    uint32_t light_words;    // dwords of the light table (miw/light.h), staged behind the tables above by the MATS_LIGHTS kernels; 0: the scene has no lights
 };
 
 // Padded bounding box of one BVH leaf (consecutive triangles in leaf order) + their 64-bit candidate mask, 32 B = 2 x b128.
@@ -108,7 +109,8 @@ __device__ __forceinline__ const float *stage_thresholds(uint4 *smem, TraceLds c
 // balls, ~82 k on the interior for ~2 k instruction slots). From LDS they are ds_reads. Unconditional for the
 // kernels that call it (the pointers must not be a choice between address spaces): the host launches those kernels only when
 // the tables fit (mi_render / mi_bvh_build), the lock-step tree kernels read the tables from global memory as before.
-template <bool WithTris>     // packet scenes (<= 64 triangles): the triangle records the shading reads, their vertex normals and texture coordinates too
+// Lights (the MATS_LIGHTS kernels): the light table follows the other tables, and SceneView::lights / constant point at the copy.
+template <bool WithTris, bool Lights = false>     // packet scenes (<= 64 triangles): the triangle records the shading reads, their vertex normals and texture coordinates too
 __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg, uint4 *smem) {
     constexpr int N = WithTris ? 10 : 7;
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + cfg.tab16);
@@ -125,6 +127,12 @@ __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg,
         for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[off + i] = src[k][i];
         off += (n + 3u) & ~3u;                                  // every table starts on a 16-byte boundary
     }
+    uint32_t *lights_at = dst + off;
+    if constexpr (Lights) {
+        const uint32_t *lsrc = reinterpret_cast<const uint32_t *>(sc.lights);
+        for (uint32_t i = threadIdx.x; i < cfg.light_words; i += blockDim.x) lights_at[i] = lsrc[i];
+        off += (cfg.light_words + 3u) & ~3u;
+    }
     // the smallest levels of the environment map's sampling hierarchy (the first steps of hier2d_sample's chain of dependent reads)
     uint32_t *env_at = dst + off;
     if (cfg.env_top_words) {
@@ -137,6 +145,13 @@ __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg,
     sc.emit_tri = reinterpret_cast<const float *>(at[3]);
     sc.emit_vnorm = reinterpret_cast<const float *>(at[4]);          // (read only for emitters whose flags say so; 0 words when absent)
     sc.emit_pmf = reinterpret_cast<const float *>(at[5]); sc.emit_cdf = reinterpret_cast<const float *>(at[6]);
+    if constexpr (Lights) {
+        if (cfg.light_words) {                                       // (0: no staged copy — the pointers stay what the host set)
+            const LightRec *staged = reinterpret_cast<const LightRec *>(lights_at);
+            if (sc.constant) sc.constant = staged + (sc.constant - sc.lights);
+            sc.lights = staged;
+        }
+    }
     if (WithTris) {                                                  // (tri_vn / tri_uv: read only for shapes whose flags say so)
         sc.tris = reinterpret_cast<const Tri *>(at[7]); sc.tri_vn = reinterpret_cast<const float *>(at[8]); sc.tri_uv = reinterpret_cast<const float *>(at[9]);
     }

@@ -30,12 +30,12 @@ MIW_HD bool direct_primary(const RenderParams &P, const SceneView &sc, LaneRegs 
         hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h.w), h.x, h.y, h.z, [ray_o]() { return ray_o; }, ray_d, si, bsdf_index, emitter);
         L.flags |= LF_VALID_RAY;                                  // :114
     }
-    else if (sc.env) emitter = (int32_t) sc.env->emitter_index;  // scene.h:248-249
+    else emitter = miss_emitter<mats_lights(Mats)>(sc);           // scene.h:248-249
     if (!P.direct.hide_emitters && emitter >= 0)                  // :119-123
-        L.res = L.res + (valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : env_eval_spec(*sc.env, ray_d, L.wl));
+        L.res = L.res + (valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : miss_eval<mats_lights(Mats)>(sc, ray_d, L.wl));
     if (!valid) return false;                                     // :125-127
     if (cnt_local) cnt_local->segments++;
-    bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);                // :132
+    bsdf = bsdf_side<mats_nested(Mats)>(sc.bsdfs, bsdf_index, si.wi);                // :132
     L.ray.o = si.p; L.ray.mint = spawn_mint(si.p);                // every further ray leaves from here
     L.ray.d = v3(0.f); L.ray.maxt = -1.f;
     return true;
@@ -47,13 +47,14 @@ MIW_HD bool direct_emitter_sample(const RenderParams &P, const SceneView &sc, La
                                   const BsdfSide &bsdf, ShadowOut &sh, Cnt *cnt_local) {
     const DirectRec &D = P.direct;
     DirectionSample ds;
-    Spec emitter_val = sample_emitter_direction<Analytic>(sc, si.p, next_2d(L.rng), ds, L.wl);   // :141-142
+    Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats)>(sc, si.p, next_2d(L.rng), ds, L.wl);   // :141-142
     if (ds.pdf == 0.f) return false;                              // :143-145
     V3 wo = to_local(si.sh, ds.d);                                // :148
     const TexCtx tc(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr, mats_full(Mats) ? sc.bsdf_tables : nullptr);
-    Spec bsdf_val = bsdf_side_eval<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, wo, tc);   // :150
-    float bsdf_pdf = bsdf_side_pdf<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, wo, tc);   // :155
-    float mis = mis_weight(ds.pdf * D.frac_lum, bsdf_pdf * D.frac_bsdf) * D.weight_lum;   // :157-158 (no delta emitters)
+    Spec bsdf_val = bsdf_side_eval<mats_full(Mats), false, mats_nested(Mats)>(bsdf, si.wi, wo, tc);   // :150
+    float bsdf_pdf = bsdf_side_pdf<mats_full(Mats), false, mats_nested(Mats)>(bsdf, si.wi, wo, tc);   // :155
+    float mis = mis_weight(ds.pdf * D.frac_lum, bsdf_pdf * D.frac_bsdf) * D.weight_lum;   // :157-158
+    if (mats_lights(Mats) && ds.delta) mis = 1.f;                 // :156
     Spec c = mis * bsdf_val * emitter_val;                        // :159
     if (all_zero(c)) return false;
     sh.has = true; sh.d = ds.d; sh.maxt = ds.dist * (1.f - MIW_SHADOW_EPSILON); sh.c = c;   // scene.cpp:203-205
@@ -67,7 +68,7 @@ MIW_HD bool direct_bsdf_sample(const SceneView &sc, LaneRegs &L, const SurfaceIn
     float s1 = next_1d(L.rng);                                    // :166-167 (Clang order: next_1d, then next_2d)
     V2 s2 = next_2d(L.rng);
     BSDFSample bs;
-    pend.bsdf_val = bsdf_side_sample<mats_full(Mats), false, Mats == MATS_NESTED>(bsdf, si.wi, s1, s2, bs, TexCtx(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr,
+    pend.bsdf_val = bsdf_side_sample<mats_full(Mats), false, mats_nested(Mats)>(bsdf, si.wi, s1, s2, bs, TexCtx(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr,
                                                                                    mats_full(Mats) ? sc.bsdf_tables : nullptr));
     if (all_zero(pend.bsdf_val)) return false;                    // :170
     pend.pdf = bs.pdf; pend.delta = (bs.sampled_type & BSDF_Delta) != 0;
@@ -77,7 +78,7 @@ MIW_HD bool direct_bsdf_sample(const SceneView &sc, LaneRegs &L, const SurfaceIn
 }
 
 // Where a BSDF-sampled ray ended, direct.cpp:177-195
-template <bool Analytic>
+template <bool Analytic, bool Lights = false>
 MIW_HD void direct_bsdf_hit(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4 h, V3 ref_p,
                             const DirectPending &pend) {
     const DirectRec &D = P.direct;
@@ -101,9 +102,9 @@ MIW_HD void direct_bsdf_hit(const RenderParams &P, const SceneView &sc, LaneRegs
             compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, h.x, h.y, h.z, ray_d, sb);
         }
     }
-    else if (sc.env) emitter = (int32_t) sc.env->emitter_index;
+    else emitter = miss_emitter<Lights>(sc);
     if (emitter < 0) return;
-    Spec emitter_val = valid ? emitter_eval(sc.emitters[emitter], sb.wi, L.wl) : env_eval_spec(*sc.env, ray_d, L.wl);   // :182
+    Spec emitter_val = valid ? emitter_eval(sc.emitters[emitter], sb.wi, L.wl) : miss_eval<Lights>(sc, ray_d, L.wl);   // :182
     float emitter_pdf = 0.f;                                      // :187-191
     if (!pend.delta) {
         // DirectionSample3f ds(si_bsdf, si), records.h:167-173 (d = -wi = ray.d for a miss)
@@ -114,7 +115,7 @@ MIW_HD void direct_bsdf_hit(const RenderParams &P, const SceneView &sc, LaneRegs
             d = d / dist;
             n = sb.sh.n;
         }
-        emitter_pdf = pdf_emitter_direction<Analytic>(sc, (uint32_t) emitter, d, dist, n, ref_p);
+        emitter_pdf = pdf_emitter_direction<Analytic, Lights>(sc, (uint32_t) emitter, d, dist, n, ref_p);
     }
     L.res = L.res + pend.bsdf_val * emitter_val * mis_weight(pend.pdf * D.frac_bsdf, emitter_pdf * D.frac_lum) * D.weight_bsdf;   // :193-196
 }
@@ -176,13 +177,13 @@ MIW_HD void pixel_stream_render_direct(const RenderParams &P, const SceneView &s
                     trace2(o, L.ray.mint, L.ray.d, L.ray.maxt, has_e, sh.d, sh.maxt, sh.has, h, occluded);
                     if (sh.has && !occluded) L.res = L.res + sh.c;     // direct.cpp:159 of the emitter sample that was in flight
                     if (has_e) {
-                        direct_bsdf_hit<Analytic>(P, sc, L, h, o, pend);
+                        direct_bsdf_hit<Analytic, mats_lights(Mats)>(P, sc, L, h, o, pend);
                         L.ray.d = v3(0.f); L.ray.maxt = -1.f;
                     }
                     if (ie == n_emitter && ib == n_bsdf) break;
                     int32_t emitter; uint32_t bsdf_index;              // more samples from this point: the interaction again
                     hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
-                    bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
+                    bsdf = bsdf_side<mats_nested(Mats)>(sc.bsdfs, bsdf_index, si.wi);
                 }
             }
         }
@@ -222,13 +223,13 @@ MIW_HD void direct_sample_ray(const RenderParams &P, const SceneView &sc, LaneRe
                 trace2(o, L.ray.mint, L.ray.d, L.ray.maxt, has_e, sh.d, sh.maxt, sh.has, h, occluded);
                 if (sh.has && !occluded) L.res = L.res + sh.c;     // direct.cpp:159 of the emitter sample that was in flight
                 if (has_e) {
-                    direct_bsdf_hit<Analytic>(P, sc, L, h, o, pend);
+                    direct_bsdf_hit<Analytic, mats_lights(Mats)>(P, sc, L, h, o, pend);
                     L.ray.d = v3(0.f); L.ray.maxt = -1.f;
                 }
                 if (ie == n_emitter && ib == n_bsdf) break;
                 int32_t emitter; uint32_t bsdf_index;              // more samples from this point: the interaction again
                 hit_surface_interaction<Analytic, mats_full(Mats)>(sc, f2u(h0.w), h0.x, h0.y, h0.z, [o0]() { return o0; }, d0, si, bsdf_index, emitter);
-                bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
+                bsdf = bsdf_side<mats_nested(Mats)>(sc.bsdfs, bsdf_index, si.wi);
             }
         }
     }

@@ -315,8 +315,12 @@ enum { STEP_CONTINUE = 0,        // extension ray queued in L.ray
 // MATS_NESTED is MATS_ALL plus the mask / blendbsdf wrappers and the null / thindielectric leaves (bsdf.h: bsdf_side<true>): the
 // class of scenes whose table holds one of those four; the other classes compile all of that out. It is also the default of the
 // entry points the CPU checker calls (lane_shade, pixel_render), which serve every table.
-enum { MATS_ALL = 0, MATS_DIFFUSE = 1, MATS_PLAIN = 2, MATS_TRIO = 3, MATS_NESTED = 4 };
-MIW_HD constexpr bool mats_full(int mats) { return mats == MATS_ALL || mats == MATS_NESTED; }   // texture coordinates, bitmaps, extended plugins
+// MATS_LIGHTS is MATS_NESTED plus the shapeless emitters (light.h; scene.h: Lights = true): the class of scenes whose emitter table
+// holds a point / spot / directional / constant record. No other class reads the light table or DirectionSample::delta.
+enum { MATS_ALL = 0, MATS_DIFFUSE = 1, MATS_PLAIN = 2, MATS_TRIO = 3, MATS_NESTED = 4, MATS_LIGHTS = 5 };
+MIW_HD constexpr bool mats_full(int mats) { return mats == MATS_ALL || mats == MATS_NESTED || mats == MATS_LIGHTS; }   // texture coordinates, bitmaps, extended plugins
+MIW_HD constexpr bool mats_nested(int mats) { return mats == MATS_NESTED || mats == MATS_LIGHTS; }   // wrapper resolution, null / thindielectric
+MIW_HD constexpr bool mats_lights(int mats) { return mats == MATS_LIGHTS; }
 // `Analytic` = false compiles the analytic-shape branch out (scenes the caller knows to be triangles only).
 template <int Mats = MATS_ALL, bool Analytic = true, typename PrevO, typename Cnt>
 MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4 h, PrevO prev_o,
@@ -332,7 +336,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     int32_t emitter = -1;                            // scene.h:243-253 (no environment emitter)
     // only MATS_ALL kernels are launched for scenes with texture coordinates (miwave.hip: diffuse_only / textured)
     if (valid) hit_surface_interaction<Analytic, mats_full(Mats)>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
-    else if (sc.env) emitter = (int32_t) sc.env->emitter_index;   // a miss sees the environment, scene.h:248-249
+    else emitter = miss_emitter<mats_lights(Mats)>(sc);   // a miss sees the environment, scene.h:248-249
     if (depth == 1 && valid) L.flags |= LF_VALID_RAY;   // path.cpp:121
     MIW_SECTION(7);                                   // (sections 6.. : the shade body of the phase machine, debug builds)
 
@@ -351,11 +355,11 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
                     d = d / dist;
                     n = si.sh.n;
                 }
-                emitter_pdf = pdf_emitter_direction<Analytic>(sc, (uint32_t) emitter, d, dist, n, ref_p);
+                emitter_pdf = pdf_emitter_direction<Analytic, mats_lights(Mats)>(sc, (uint32_t) emitter, d, dist, n, ref_p);
             }
             emission_weight = mis_weight(L.prev_pdf, emitter_pdf);
         }
-        Spec radiance = valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : env_eval_spec(*sc.env, ray_d, L.wl);
+        Spec radiance = valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : miss_eval<mats_lights(Mats)>(sc, ray_d, L.wl);
         L.res = L.res + emission_weight * L.tp * radiance;
     }
 
@@ -375,7 +379,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     if (cnt_local) cnt_local->segments++;
     BsdfSide bsdf;                                                   // si.bsdf(ray), incl. the twosided adapter
     if (Mats == MATS_DIFFUSE) { bsdf.b = sc.bsdfs + bsdf_index; bsdf.flip = bsdf.none = false; bsdf.flags = BSDF_DiffuseReflection; }
-    else bsdf = bsdf_side<Mats == MATS_NESTED>(sc.bsdfs, bsdf_index, si.wi);
+    else bsdf = bsdf_side<mats_nested(Mats)>(sc.bsdfs, bsdf_index, si.wi);
     const uint32_t bflags = bsdf.flags;
     L.ray.o = si.p; L.ray.mint = spawn_mint(si.p);   // shared by shadow + extension ray
     L.ray.d = v3(0.f); L.ray.maxt = -1.f;
@@ -384,17 +388,17 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     const TexCtx tc(L.wl, si.uv, mats_full(Mats) ? sc.bitmaps : nullptr, mats_full(Mats) ? sc.bsdf_tables : nullptr);
     constexpr bool Ext = mats_full(Mats);            // plugins only "extended" scenes contain (roughplastic)
     constexpr bool Trio = Mats == MATS_TRIO;
-    constexpr bool Nested = Mats == MATS_NESTED;     // wrapper resolution, null / thindielectric
+    constexpr bool Nested = mats_nested(Mats);       // wrapper resolution, null / thindielectric
 
     // ---- emitter sampling, :155-172 ----
     if (bflags & BSDF_Smooth) {
         DirectionSample ds;
-        Spec emitter_val = sample_emitter_direction<Analytic>(sc, si.p, next_2d(L.rng), ds, L.wl);
+        Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats)>(sc, si.p, next_2d(L.rng), ds, L.wl);
         if (ds.pdf != 0.f) {
             V3 wo = to_local(si.sh, ds.d);
             Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_eval(*bsdf.b, si.wi, wo, tc) : bsdf_side_eval<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
             float bpdf = Mats == MATS_DIFFUSE ? diffuse_pdf(si.wi, wo) : bsdf_side_pdf<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
-            float mis = mis_weight(ds.pdf, bpdf);
+            float mis = (mats_lights(Mats) && ds.delta) ? 1.f : mis_weight(ds.pdf, bpdf);   // path.cpp:170
             Spec c = mis * L.tp * bsdf_val * emitter_val;
             if (!all_zero(c)) {
                 // shadow ray, scene.cpp:203-205

@@ -8,6 +8,7 @@
 #include "shape.h"
 #include "bsdf.h"
 #include "envmap.h"
+#include "light.h"
 
 namespace miw {
 
@@ -41,9 +42,10 @@ struct EmitterRec {
     float sum, normalization;
     uint32_t flags;      // bit0: emit_vnorm valid for this emitter; bit1: the shape is analytic rectangle `tri_first`
                          // (no face tables; normalization = its 1 / surface area)
-    uint32_t type;       // 0: area light on `shape`; 1: the environment map (SceneView::env)
+    uint32_t type;       // 0: area light on `shape`; 1: the environment map (SceneView::env); 2 .. 5: a light (light.h), `tri_first`
+                         // indexes SceneView::lights — no shape, no face tables
 };
-enum : uint32_t { EMITTER_AREA = 0, EMITTER_ENVMAP = 1 };
+// (EmitterRec::type: the EMITTER_* values are defined in light.h)
 enum : uint32_t { SHAPE_HAS_NORMALS = 1u, SHAPE_HAS_TEXCOORDS = 8u };     // ShapeRec::flags (= MI_SHAPE_* of include/miwave.h)
 
 struct SceneView {
@@ -68,6 +70,9 @@ struct SceneView {
     const struct Bvh4Node *nodes4;                  // device only: the 4-wide quantised tree the phase machine walks (bvh4.h) or nullptr
     const struct Bvh8Node *nodes8;                  // device only: the 8-wide quantised tree (bvh8.h) of a view whose tris / tri_vn are in that tree's order, or nullptr
     const float *env_top; uint32_t env_top_count, env_top_base;   // device only: the environment warp's top levels in LDS (envmap.h: EnvTop); count 0: none
+    const LightRec *lights;                         // point / spot / directional / constant emitters (EmitterRec::tri_first indexes this table) or nullptr;
+    const LightRec *constant;                       // the constant environment emitter among them or nullptr: what a miss sees in a scene without envmap.
+                                                    // Read only by code compiled with Lights = true (below); the classes of scenes without lights never touch either
 };
 MIW_HD EnvTop env_top(const SceneView &sc) { EnvTop t; t.p = sc.env_top; t.count = sc.env_top_count; t.base = sc.env_top_base; return t; }
 MIW_HD void scene_view_prepare(SceneView &v) {
@@ -100,7 +105,15 @@ MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float
     emitter = shape.emitter; bsdf_index = shape.bsdf;
 }
 
-struct DirectionSample { V3 p, n, d; float dist, pdf; uint32_t emitter; };
+struct DirectionSample { V3 p, n, d; float dist, pdf; uint32_t emitter; bool delta; };   // delta: written and read by Lights = true code only
+
+// si.emitter(scene) of a ray that hit nothing (scene.h:248-249): the environment emitter — the environment map or, with Lights, the constant one
+template <bool Lights = false>
+MIW_HD int32_t miss_emitter(const SceneView &sc) {
+    if (sc.env) return (int32_t) sc.env->emitter_index;
+    if (Lights && sc.constant) return (int32_t) sc.constant->emitter_index;
+    return -1;
+}
 
 MIW_HD MeshSampler emitter_mesh(const SceneView &sc, const EmitterRec &e) {
     MeshSampler m;
@@ -115,12 +128,7 @@ MIW_HD MeshSampler emitter_mesh(const SceneView &sc, const EmitterRec &e) {
 }
 
 // ---- Sphere as an emitter shape: sphere.cpp:146-275 -----------------------------------------------------------
-// warp.h:255-260 (circ(z) = sqrt(1 - z^2), frozen as safe_sqrt(fnmadd(z, z, 1)))
-MIW_HD V3 square_to_uniform_sphere(V2 sample) {
-    float z = fnmadd(2.f, sample.y, 1.f), r = safe_sqrt(fnmadd(z, z, 1.f)), s, c;
-    sincos_((2.f * MIW_PI) * sample.x, s, c);
-    return v3(r * c, r * s, z);
-}
+// (square_to_uniform_sphere: light.h)
 // Sphere::sample_direction (:169-246): uniform over the cone the sphere subtends from outside, over the surface from
 // inside. Fills ds.p, ds.n, ds.d, ds.dist, ds.pdf.
 MIW_HD void sphere_sample_direction(const AnalyticRec &r, V3 ref_p, V2 sample, DirectionSample &ds) {
@@ -234,12 +242,18 @@ MIW_HD Spec env_eval_spec(const EnvmapRec &e, V3 d, const Wavelengths &) { retur
 // Endpoint::sample_direction of emitter `index` (endpoint.h:119-139): AreaLight (area.cpp:121-166 +
 // shape.cpp:292-309) or the environment map (envmap.cpp:157-190). Returns radiance / pdf; `ds.pdf == 0`: no sample.
 // Analytic = false: the caller knows the scene to hold no analytic shapes, hence no sphere / rectangle lights (their code is compiled out).
-template <bool Analytic = true>
+// Lights = true: the table may hold point / spot / directional / constant records (light.h); false compiles them out.
+template <bool Analytic = true, bool Lights = false>
 MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     const EmitterRec &e = sc.emitters[index];
     Spec value;
     ds.emitter = index;
-    if (e.type == EMITTER_ENVMAP) {
+    if (Lights) ds.delta = false;
+    if (Lights && e.type >= EMITTER_POINT) {
+        LightSample ls;
+        value = light_sample_direction(sc.lights[e.tri_first], ref_p, sample, ls, wl);
+        ds.p = ls.p; ds.n = ls.n; ds.d = ls.d; ds.dist = ls.dist; ds.pdf = ls.pdf; ds.delta = ls.delta;
+    } else if (e.type == EMITTER_ENVMAP) {
         value = env_sample_direction_spec(*sc.env, ref_p, sample, ds.d, ds.dist, ds.pdf, ds.p, ds.n, wl, env_top(sc));
     } else {
         if (Analytic && (e.flags & 2u) && sc.rects[e.tri_first].kind == ANALYTIC_SPHERE) {
@@ -267,10 +281,11 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
 // scene.cpp:164-200, *without* the visibility test (the shadow ray is a separate stage of the kernels;
 // mi_sample_emitter_direction traces it on request). Returns the unoccluded emitter value; `ds.pdf == 0`
 // means "no sample" (path.cpp:160).
-template <bool Analytic = true>
+template <bool Analytic = true, bool Lights = false>
 MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     if (sc.emitter_count == 0) {                       // scene.cpp:208-211
         ds.p = ds.n = ds.d = v3(0.f); ds.dist = 0.f; ds.pdf = 0.f; ds.emitter = 0;
+        if (Lights) ds.delta = false;
         return spec(0.f);
     }
     uint32_t index = 0;
@@ -282,7 +297,7 @@ MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, D
         index = i < sc.emitter_count - 1 ? i : sc.emitter_count - 1;
         sample.x = (sample.x - (float) index * emitter_pdf) * n;
     }
-    Spec value = emitter_sample_direction<Analytic>(sc, index, ref_p, sample, ds, wl);
+    Spec value = emitter_sample_direction<Analytic, Lights>(sc, index, ref_p, sample, ds, wl);
     if (sc.emitter_count > 1) {                        // scene.cpp:195-197
         ds.pdf *= emitter_pdf;
         value = value * rcp(emitter_pdf);
@@ -293,9 +308,10 @@ MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, D
 // Endpoint::pdf_direction of emitter `emitter` (area.cpp:168-187 + shape.cpp:311-323, envmap.cpp:192-208).
 // `ds_d`, `ds_dist`, `ds_n` come from DirectionSample(si_bsdf, si) (records.h:167-173).
 // `ref_p` = it.p, the point the direction leaves from (only the sphere's pdf_direction needs it).
-template <bool Analytic = true>
+template <bool Analytic = true, bool Lights = false>
 MIW_HD float emitter_pdf_direction(const SceneView &sc, uint32_t emitter, V3 ds_d, float ds_dist, V3 ds_n, V3 ref_p) {
     const EmitterRec &e = sc.emitters[emitter];
+    if (Lights && e.type >= EMITTER_POINT) return light_pdf_direction(sc.lights[e.tri_first]);
     if (e.type == EMITTER_ENVMAP) return env_pdf_direction(*sc.env, ds_d);
     float dp = dot(ds_d, ds_n);
     bool active = dp < 0.f;
@@ -310,9 +326,9 @@ MIW_HD float emitter_pdf_direction(const SceneView &sc, uint32_t emitter, V3 ds_
     return active ? pdf : 0.f;
 }
 // scene.cpp:216-231
-template <bool Analytic = true>
+template <bool Analytic = true, bool Lights = false>
 MIW_HD float pdf_emitter_direction(const SceneView &sc, uint32_t emitter, V3 ds_d, float ds_dist, V3 ds_n, V3 ref_p) {
-    float value = emitter_pdf_direction<Analytic>(sc, emitter, ds_d, ds_dist, ds_n, ref_p);
+    float value = emitter_pdf_direction<Analytic, Lights>(sc, emitter, ds_d, ds_dist, ds_n, ref_p);
     if (sc.emitter_count > 1) value = value * sc.emitter_count_inv;
     return value;
 }
@@ -320,6 +336,12 @@ MIW_HD float pdf_emitter_direction(const SceneView &sc, uint32_t emitter, V3 ds_
 // AreaLight::eval, area.cpp:63-71
 MIW_HD Spec emitter_eval(const EmitterRec &e, V3 wi, const Wavelengths &wl) {
     return wi.z > 0.f ? tex_eval(e.radiance, wl) : spec(0.f);
+}
+// Endpoint::eval of the environment emitter a miss sees (miss_emitter() >= 0): envmap.cpp:134-147 or, with Lights, constant.cpp:61-65
+template <bool Lights = false>
+MIW_HD Spec miss_eval(const SceneView &sc, V3 ray_d, const Wavelengths &wl) {
+    if (Lights && !sc.env) return light_eval(*sc.constant, wl);
+    return env_eval_spec(*sc.env, ray_d, wl);
 }
 
 

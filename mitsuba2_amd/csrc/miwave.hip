@@ -25,6 +25,9 @@
 #include <algorithm>
 
 #include "../../include/miwave.h"
+#if defined(MIW_NESTED_PART) || defined(MIW_LIGHTS_PART)   /* miwave_nested.hip, miwave_lights.hip: the kernel headers alone */
+#define MIW_KERNELS_ONLY 1
+#endif
 // Section clock (debug builds, -DMIW_SECTION_PROFILE=1): wall cycles per wavefront between markers, summed
 // into g_sections and printed by mi_render when MIW_DEBUG is set. Not compiled into the product library.
 #if defined(MIW_SECTION_PROFILE)
@@ -57,7 +60,7 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "miw/bvh.h"
 #include "miw/path.h"
 #include "miw/direct.h"
-#if defined(MIW_NESTED_PART)            /* miwave_nested.hip: the path kernels alone (device/nested_instances.h); the library's other kernels have one definition, here */
+#if defined(MIW_KERNELS_ONLY)            /* miwave_nested.hip: the path kernels alone (device/nested_instances.h); the library's other kernels have one definition, here */
 #include "miw/bvh4.h"
 #include "miw/bvh8.h"
 #define MIW_KERNEL static __global__    /* ... and those of their headers that are no templates stay out of its objects */
@@ -96,7 +99,7 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/wavefront_kernels.h"
 #include "device/resident_kernel.h"
 #include "device/phased_kernel.h"
-#if !defined(MIW_NESTED_PART)
+#if !defined(MIW_KERNELS_ONLY)
 #if !MIW_SPECTRAL
 #include "device/pooled_kernel.h"      /* (experimental, opt-in: the scalar_rgb library only) */
 #endif
@@ -106,8 +109,9 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/eval_kernels.h"
 #include "device/sample_kernel.h"
 #include "device/nested_instances.h"   /* a split build (-DMIW_SPLIT_NESTED=1) compiles the MATS_NESTED kernels in miwave_nested.hip */
+#include "device/lights_instances.h"   /* ... and (-DMIW_SPLIT_LIGHTS=1) the MATS_LIGHTS kernels in miwave_lights.hip */
 
-#if !defined(MIW_NESTED_PART)           /* (miwave_nested.hip includes this file for the kernels above alone) */
+#if !defined(MIW_KERNELS_ONLY)           /* (miwave_nested.hip includes this file for the kernels above alone) */
 __global__ void k_iota(uint32_t *out, uint32_t n) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = i; }
 
 // ---------------------------------------------------------------------------------------
@@ -214,6 +218,8 @@ struct mi_ctx {
     bool textured = false;                                   // texture coordinates, bitmaps or an "extended" plugin: MATS_ALL kernels
     std::vector<float> bsdf_tables; DevBuf<float> d_bsdf_tables;
     std::vector<EmitterRec> emitters;
+    std::vector<LightRec> lights; DevBuf<LightRec> d_lights; int32_t constant_light = -1;   // point / spot / directional / constant emitters (miw/light.h); index of the constant one
+    bool lights_on = false;                                  // the emitter table holds a light: MATS_LIGHTS kernels (nested and textured are set too)
     std::vector<float> emit_tri, emit_vnorm, emit_pmf, emit_cdf;
     bool have_scene = false, have_bvh = false;
 
@@ -305,7 +311,7 @@ void mi_destroy(mi_ctx *c) {
     (void) hipSetDevice(c->device);
     (void) hipDeviceSynchronize();
     c->d_nodes.release(); c->d_tris.release(); c->d_tri_vn.release(); c->d_tri_uv.release(); c->d_bitmap_data.release(); c->d_bitmaps.release(); c->d_bsdf_tables.release(); c->d_shapes.release(); c->d_rects.release(); c->d_bsdfs.release();
-    c->d_emitters.release(); c->d_leaf_boxes.release(); c->d_tri_bounds.release(); c->d_nodes4.release(); c->d_nodes8.release(); c->d_tris8.release(); c->d_tri_vn8.release(); c->d_env_data.release(); c->d_env_levels.release(); c->d_env.release(); c->d_emit_tri.release(); c->d_emit_vnorm.release(); c->d_emit_pmf.release(); c->d_emit_cdf.release();
+    c->d_emitters.release(); c->d_lights.release(); c->d_leaf_boxes.release(); c->d_tri_bounds.release(); c->d_nodes4.release(); c->d_nodes8.release(); c->d_tris8.release(); c->d_tri_vn8.release(); c->d_env_data.release(); c->d_env_levels.release(); c->d_env.release(); c->d_emit_tri.release(); c->d_emit_vnorm.release(); c->d_emit_pmf.release(); c->d_emit_cdf.release();
     c->q_tp.release(); c->q_res.release(); c->q_ray_o.release(); c->q_ray_d.release(); c->q_hit.release();
     c->q_sh_d.release(); c->q_sh_c.release(); c->q_st.release(); c->q_pos.release(); c->q_pixel.release(); c->q_sh_vis.release();
     c->d_accum.release(); c->d_out.release(); c->d_next_pixel.release(); c->d_lane_cost.release(); c->d_cost_sorted.release(); c->d_lane_iota.release(); c->d_lane_sorted.release(); c->d_place_tmp.release(); c->d_piece_list.release(); c->d_simd_ids.release(); c->d_lists.release(); c->d_list_counts.release(); c->d_block_ids.release(); c->d_tile_list.release(); c->d_cnt.release();
@@ -440,6 +446,43 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     if (!s->bsdfs || s->bsdf_count == 0) return fail(c, MI_ERR_INVALID, "scene: no bsdfs");
     if (s->face_count >= (1u << 27) - 16u) return fail(c, MI_ERR_INVALID, "scene: too many faces");   // leaf codes (first << 4 | count - 1) must stay clear of MIW_BVH4_ABSENT / MIW_WALK_DONE
 
+    // Scene::m_emitters order: the environment map and the lights sit at their emitter_index, the area emitters fill the other slots in order
+    if (s->light_count && !s->lights) return fail(c, MI_ERR_INVALID, "scene: light_count without lights");
+    const uint32_t emitter_total = s->emitter_count + (s->envmap ? 1u : 0u) + s->light_count;
+    std::vector<int32_t> slot_light(emitter_total, -1);        // slot -> light record, -2: the environment map, -1: an area emitter
+    std::vector<int32_t> area_slot(s->emitter_count, -1);
+    if (s->envmap && s->envmap->emitter_index >= emitter_total) return fail(c, MI_ERR_INVALID, "envmap: emitter_index out of range");
+    if (s->light_count) {
+        if (s->envmap) slot_light[s->envmap->emitter_index] = -2;
+        int32_t constant = -1;
+        for (uint32_t k = 0; k < s->light_count; ++k) {
+            const mi_light &l = s->lights[k];
+            if (l.type > MI_LIGHT_CONSTANT) return fail(c, MI_ERR_INVALID, "light %u: unknown type %u", k, l.type);
+            if (l.emitter_index >= emitter_total) return fail(c, MI_ERR_INVALID, "light %u: emitter_index %u leaves a gap in the emitter list (%u emitters)", k, l.emitter_index, emitter_total);
+            if (slot_light[l.emitter_index] != -1) return fail(c, MI_ERR_INVALID, "light %u: emitter_index %u collides with %s", k, l.emitter_index, slot_light[l.emitter_index] == -2 ? "the envmap" : "another light");
+            slot_light[l.emitter_index] = (int32_t) k;
+            if (l.type == MI_LIGHT_CONSTANT) {
+                if (s->envmap) return fail(c, MI_ERR_INVALID, "light %u: a constant emitter together with an envmap (one environment emitter per scene)", k);
+                if (constant >= 0) return fail(c, MI_ERR_INVALID, "light %u: a second constant emitter (light %d is one; one environment emitter per scene)", k, constant);
+                constant = (int32_t) k;
+            }
+            if (l.type == MI_LIGHT_SPOT && l.value_tex.type == MI_TEX_BITMAP) return fail(c, MI_ERR_INVALID, "light %u: a spot emitter with a texture child is not supported", k);
+            if (l.type == MI_LIGHT_SPOT && !(l.cutoff_angle >= l.beam_width)) return fail(c, MI_ERR_INVALID, "light %u: spot: cutoff_angle must not be below beam_width", k);
+            if (l.type == MI_LIGHT_DIRECTIONAL) {
+                const float n2 = l.direction[0] * l.direction[0] + l.direction[1] * l.direction[1] + l.direction[2] * l.direction[2];
+                if (!(std::fabs(n2 - 1.f) <= 1e-4f)) return fail(c, MI_ERR_INVALID, "light %u: directional: direction is not of unit length", k);
+            }
+            if ((l.type == MI_LIGHT_DIRECTIONAL || l.type == MI_LIGHT_CONSTANT) && !(l.bsphere_radius >= 0.f && isfinite_(l.bsphere_radius)))
+                return fail(c, MI_ERR_INVALID, "light %u: bsphere_radius must be finite and not negative", k);
+#if MIW_SPECTRAL
+            if (l.value_tex.type != MI_TEX_D65 && l.value_tex.type != MI_TEX_SRGB_D65 && l.value_tex.type != MI_TEX_UNIFORM)
+                return fail(c, MI_ERR_INVALID, "light %u: the scalar_spectral library needs a spectral value record", k);
+#endif
+        }
+        uint32_t slot = 0;
+        for (uint32_t i = 0; i < s->emitter_count; ++i) { while (slot_light[slot] != -1) ++slot; area_slot[i] = (int32_t) slot++; }
+    }
+
     c->tris_in.assign(s->face_count, Tri{});
     std::vector<uint32_t> face_shape(s->face_count, 0xffffffffu);
     bool any_normals = false;
@@ -448,7 +491,6 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
         const mi_shape &sh = s->shapes[i];
         if (sh.bsdf >= s->bsdf_count) return fail(c, MI_ERR_INVALID, "shape %u: bsdf index out of range", i);
         if (sh.emitter >= (int32_t) s->emitter_count) return fail(c, MI_ERR_INVALID, "shape %u: emitter index out of range", i);
-        if (s->envmap && s->envmap->emitter_index > s->emitter_count) return fail(c, MI_ERR_INVALID, "envmap: emitter_index out of range");
         if ((uint64_t) sh.first_face + sh.face_count > s->face_count) return fail(c, MI_ERR_INVALID, "shape %u: face range out of bounds", i);
         if ((sh.flags & MI_SHAPE_HAS_NORMALS) && !s->vertex_normals) return fail(c, MI_ERR_INVALID, "shape %u: HAS_NORMALS without vertex_normals", i);
         for (uint32_t f = sh.first_face; f < sh.first_face + sh.face_count; ++f) {
@@ -457,7 +499,8 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
         }
         // emitter ids index the combined list: the environment map sits at envmap->emitter_index
         int32_t emitter_id = sh.emitter;
-        if (emitter_id >= 0 && s->envmap && (uint32_t) emitter_id >= s->envmap->emitter_index) emitter_id += 1;
+        if (emitter_id >= 0 && s->light_count) emitter_id = area_slot[emitter_id];
+        else if (emitter_id >= 0 && s->envmap && (uint32_t) emitter_id >= s->envmap->emitter_index) emitter_id += 1;
         ShapeRec r; r.bsdf = sh.bsdf; r.emitter = emitter_id; r.flags = sh.flags & (MI_SHAPE_HAS_NORMALS | MI_SHAPE_HAS_TEXCOORDS); r.pad = 0;
         if (sh.flags & (MI_SHAPE_RECTANGLE | MI_SHAPE_SPHERE)) {
             if (sh.face_count != 1) return fail(c, MI_ERR_INVALID, "shape %u: an analytic shape is one primitive (face_count == 1)", i);
@@ -558,8 +601,28 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     c->emitters.clear(); c->emit_tri.clear(); c->emit_vnorm.clear(); c->emit_pmf.clear(); c->emit_cdf.clear();
     bool any_emit_normals = false;
     auto push_env = [&]() { EmitterRec r; memset(&r, 0, sizeof r); r.type = EMITTER_ENVMAP; r.shape = 0xffffffffu; c->emitters.push_back(r); };
+    c->lights.clear(); c->constant_light = -1; c->lights_on = s->light_count != 0;
+    auto push_light = [&](uint32_t k) {                        // an emitter record without shape and face tables: `tri_first` = its light record
+        const mi_light &l = s->lights[k];
+        LightRec q; memset(&q, 0, sizeof q);
+#if MIW_SPECTRAL
+        memcpy(&q.value, &l.value_tex, sizeof(TexRec));
+#else
+        q.value.type = TEX_RGB; memcpy(q.value.v, l.value, 12);
+#endif
+        q.type = EMITTER_POINT + l.type; q.emitter_index = (uint32_t) c->emitters.size();
+        memcpy(q.position, l.position, 12); memcpy(q.direction, l.direction, 12); memcpy(q.to_object, l.to_object, 64);
+        q.cutoff_angle = l.cutoff_angle; q.cos_cutoff_angle = l.cos_cutoff_angle; q.cos_beam_width = l.cos_beam_width; q.inv_transition_width = l.inv_transition_width;
+        q.dist = 2.f * light_bsphere_radius(l.bsphere_radius);
+        EmitterRec r; memset(&r, 0, sizeof r); r.type = q.type; r.shape = 0xffffffffu; r.tri_first = (uint32_t) c->lights.size();
+        if (l.type == MI_LIGHT_CONSTANT) c->constant_light = (int32_t) c->lights.size();
+        c->lights.push_back(q); c->emitters.push_back(r);
+    };
+    // (with lights: every slot before an area emitter's own that the environment map or a light takes)
+    auto push_specials = [&]() { while (c->emitters.size() < emitter_total && slot_light[c->emitters.size()] != -1) { const int32_t k = slot_light[c->emitters.size()]; if (k == -2) push_env(); else push_light((uint32_t) k); } };
     for (uint32_t i = 0; i < s->emitter_count; ++i) {
-        if (s->envmap && s->envmap->emitter_index == i) push_env();
+        if (s->light_count) push_specials();
+        else if (s->envmap && s->envmap->emitter_index == i) push_env();
         const mi_emitter &e = s->emitters[i];
         if (e.shape >= s->shape_count) return fail(c, MI_ERR_INVALID, "emitter %u: shape index out of range", i);
         const mi_shape &sh = s->shapes[e.shape];
@@ -604,7 +667,9 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
         c->emitters.push_back(r);
     }
     if (!any_emit_normals) c->emit_vnorm.clear();
-    if (s->envmap && s->envmap->emitter_index >= s->emitter_count) push_env();
+    if (s->light_count) push_specials();
+    else if (s->envmap && s->envmap->emitter_index >= s->emitter_count) push_env();
+    if (c->lights_on) { c->nested = c->textured = true; c->diffuse_only = c->trio = false; }    // -> the MATS_LIGHTS kernels (the MATS_NESTED table + miw/light.h)
 
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_env = false;
@@ -629,6 +694,7 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     HIP_TRY(c, c->d_rects.upload(c->rects, c->stream));
     HIP_TRY(c, c->d_bsdfs.upload(c->bsdfs, c->stream));
     HIP_TRY(c, c->d_emitters.upload(c->emitters, c->stream));
+    HIP_TRY(c, c->d_lights.upload(c->lights, c->stream));
     HIP_TRY(c, c->d_emit_tri.upload(c->emit_tri, c->stream));
     HIP_TRY(c, c->d_emit_vnorm.upload(c->emit_vnorm, c->stream));
     HIP_TRY(c, c->d_emit_pmf.upload(c->emit_pmf, c->stream));
@@ -653,6 +719,7 @@ static size_t lds_table_bytes(const mi_ctx *c, uint32_t words[10], bool with_tri
     words[8] = with_tris ? (uint32_t) c->tri_vn_in.size() : 0u; words[9] = with_tris ? (uint32_t) c->tri_uv_in.size() : 0u;
     size_t total = 0;
     for (int k = 0; k < 10; ++k) total += ((size_t) words[k] + 3u) / 4u * 16u;
+    total += c->lights.size() * sizeof(LightRec);             // the light table behind them (TraceLds::light_words; sizeof(LightRec) is a multiple of 16)
     return total;
 }
 
@@ -934,6 +1001,8 @@ mi_status mi_bvh_build(mi_ctx *c, int32_t quality) {
     v.emit_tri = c->d_emit_tri.p; v.emit_vnorm = c->emit_vnorm.empty() ? nullptr : c->d_emit_vnorm.p;
     v.emit_pmf = c->d_emit_pmf.p; v.emit_cdf = c->d_emit_cdf.p;
     v.env = c->have_env ? c->d_env.p : nullptr;
+    v.lights = c->lights.empty() ? nullptr : c->d_lights.p;
+    v.constant = c->constant_light >= 0 ? c->d_lights.p + c->constant_light : nullptr;
     v.env_top = nullptr; v.env_top_count = v.env_top_base = 0;      // (set inside the kernels that stage them: trace.h stage_tables)
     v.rects = c->rects.empty() ? nullptr : c->d_rects.p; v.rect_count = (uint32_t) c->rects.size();
 
@@ -1220,7 +1289,9 @@ static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO 
     // the instantiation mi_render would pick for this scene: no BSDF dispatch when every shape is plain diffuse, no texture lookups
     // without texture coordinates, no analytic shapes where there are none
     if (direct) {
-        if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_DIRECT);
+        if (tiny && c->lights_on) MIW_SAMPLE_LAUNCH(1, MATS_LIGHTS, false, INTEG_DIRECT);
+        else if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_DIRECT);
+        else if (c->lights_on) MIW_SAMPLE_LAUNCH(0, MATS_LIGHTS, true, INTEG_DIRECT);
         else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_DIRECT);
         else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_DIRECT);
         else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_DIRECT);
@@ -1229,7 +1300,9 @@ static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO 
     }
     else if (tiny && c->diffuse_only && small) MIW_SAMPLE_LAUNCH(2, MATS_DIFFUSE, false, INTEG_PATH);
     else if (tiny && c->diffuse_only) MIW_SAMPLE_LAUNCH(1, MATS_DIFFUSE, false, INTEG_PATH);
+    else if (tiny && c->lights_on) MIW_SAMPLE_LAUNCH(1, MATS_LIGHTS, false, INTEG_PATH);
     else if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_PATH);
+    else if (c->lights_on) MIW_SAMPLE_LAUNCH(0, MATS_LIGHTS, true, INTEG_PATH);
     else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_PATH);
     else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_PATH);
     else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_PATH);
@@ -1832,6 +1905,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     // measured on MI355X: the resident plan wins whenever the scene query runs out of LDS
     // (packets / staged tree) or with the LDS-stack walk; the queue plan remains for the stackless fallback
     if (plan == 0) plan = (lds_resident || c->lds_cfg.stack || c->nested) ? 2 : 1;
+    if (plan == 1 && c->lights_on) return fail(c, MI_ERR_INVALID, "render: scenes with point / spot / directional / constant emitters run the resident plan only (plan 0 or 2)");
     if (plan == 1 && c->nested) return fail(c, MI_ERR_INVALID, "render: scenes with mask / blendbsdf / null / thindielectric records run the resident plan only (plan 0 or 2)");
 #if MIW_SPECTRAL
     if (cfg->plan == 1) return fail(c, MI_ERR_INVALID, "render: the scalar_spectral library runs the resident plan only (plan 0 or 2)");
@@ -1888,6 +1962,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         if (rec16) L.rlds = (size_t) L.cfg.thr16 * 16 + (MIW_FC_TABLE + 3) / 4 * 16;
         L.cfg.tab16 = (uint32_t) ((L.rlds + 15) / 16);
         L.table_bytes = lds_table_bytes(c, L.cfg.tab_words, c->lds_cfg.brute != 0);
+        L.cfg.light_words = (uint32_t) (c->lights.size() * sizeof(LightRec) / 4);
         // (packet scenes always stage: mi_bvh_build bounded their tables by 24 KB, which with the packets, boxes and thresholds stays
         // inside the 64 KB a workgroup may ask for — at fewer workgroups per CU past 40 KB)
         L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u : lds_budget);
@@ -2050,9 +2125,13 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_ALL, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_ALL, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_LIGHTS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_LIGHTS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_LIGHTS, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
                 HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_LIGHTS, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
             }
         }
         const uint32_t sync_every = 8;
@@ -2210,7 +2289,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #define MIW_POOLED_LAUNCH_(M, A, NW_, PP_) do { HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
                                      MIW_TIMED(6, hipLaunchKernelGGL((k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } while (0)
 #define MIW_POOLED_LAUNCH(M, A) do { if (pool_pp == 2) MIW_POOLED_LAUNCH_(M, A, 8, 2); else MIW_POOLED_LAUNCH_(M, A, 12, 1); } while (0)
-                    if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
+                    if (c->lights_on) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with point / spot / directional / constant emitters");
+                    else if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
                     else if (c->textured) MIW_POOLED_LAUNCH_(MATS_ALL, true, 12, 1);
                     else if (trio_kernel) MIW_POOLED_LAUNCH(MATS_TRIO, false);
                     else if (c->rects.empty()) MIW_POOLED_LAUNCH_(MATS_PLAIN, false, 12, 1);
@@ -2222,25 +2302,29 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #endif
                 else
                 if (phased8 && place) {
-                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, true);
+                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 2, true);
+                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, true);
                     else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, true);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, true);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, true);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, true);
                 } else if (phased8) {
-                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, false);
+                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 2, false);
+                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, false);
                     else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, false);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, false);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, false);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, false);
                 } else if (phased && place) {                           // a shard of about one pixel per resident lane: the Placed instantiations (measuring, then placed launch)
-                    if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 1, true);
+                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 1, true);
+                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 1, true);
                     else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 1, true);
                     else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 1, true);
                     else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 1, true);
                     else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 1, true);
                 } else if (phased) {
                     if (!c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);
+                    else if (c->lights_on) MIW_PHASED_LAUNCH(MATS_LIGHTS, true, 1);
                     else if (c->nested) MIW_PHASED_LAUNCH(MATS_NESTED, true, 1);
                     else if (c->textured) MIW_PHASED_LAUNCH(MATS_ALL, true, 1);
                     else if (trio_kernel) MIW_PHASED_LAUNCH(MATS_TRIO, false, 1);
@@ -2251,7 +2335,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 #undef MIW_PHASED_LAUNCH_
                 else if (direct) {
 #define MIW_DIRECT_LAUNCH(T, M, A) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, INTEG_DIRECT>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
-                    if (tiny && c->nested) MIW_DIRECT_LAUNCH(1, MATS_NESTED, false);
+                    if (tiny && c->lights_on) MIW_DIRECT_LAUNCH(1, MATS_LIGHTS, false);
+                    else if (tiny && c->nested) MIW_DIRECT_LAUNCH(1, MATS_NESTED, false);
+                    else if (c->lights_on) MIW_DIRECT_LAUNCH(0, MATS_LIGHTS, true);
                     else if (c->nested) MIW_DIRECT_LAUNCH(0, MATS_NESTED, true);
                     else if (tiny && c->textured) MIW_DIRECT_LAUNCH(1, MATS_ALL, false);
                     else if (tiny) MIW_DIRECT_LAUNCH(1, MATS_PLAIN, false);
@@ -2267,7 +2353,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (tiny && c->diffuse_only && c->view.tri_count <= 32u) MIW_PATH_LAUNCH(2, MATS_DIFFUSE);   // 32-bit candidate masks (BASELINE config 2: 32 triangles)
                 else if (tiny && c->diffuse_only) MIW_PATH_LAUNCH(1, MATS_DIFFUSE);
+                else if (tiny && c->lights_on) MIW_PATH_LAUNCH(1, MATS_LIGHTS);
                 else if (tiny && c->nested) MIW_PATH_LAUNCH(1, MATS_NESTED);          // + wrapper resolution, null / thindielectric
+                else if (c->lights_on) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_LIGHTS, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (c->nested) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_NESTED, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (tiny && c->textured) MIW_PATH_LAUNCH(1, MATS_ALL);           // texture coordinates / bitmap lookups compiled in
                 else if (!tiny && c->textured) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_ALL, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
@@ -2276,12 +2364,20 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 else if (c->rects.empty()) MIW_PATH_LAUNCH(0, MATS_PLAIN);
                 else MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_PLAIN, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
 #undef MIW_PATH_LAUNCH
-            } else if (c->nested && direct && tiny)
+            } else if (c->lights_on && direct && tiny)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_LIGHTS, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->nested && direct && tiny)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->lights_on && direct)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_LIGHTS, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
             else if (c->nested && direct)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->lights_on && tiny)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_LIGHTS>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
             else if (c->nested && tiny)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+            else if (c->lights_on)
+                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_LIGHTS>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
             else if (c->nested)
                 MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
             else if (direct && tiny)
@@ -2480,4 +2576,4 @@ mi_status mi_selftest(mi_ctx *c, int32_t which, uint64_t *mismatches) {
 }
 
 } // extern "C"
-#endif // !MIW_NESTED_PART
+#endif // !MIW_KERNELS_ONLY

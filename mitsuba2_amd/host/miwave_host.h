@@ -421,6 +421,27 @@ private:
     std::vector<float> m_data, m_density;
 };
 
+// The emitters without a shape: src/emitters/point.cpp, spot.cpp, directional.cpp, constant.cpp. A Light holds the record the
+// plugin's constructor derives from its properties (include/miwave.h: mi_light); Scene::build adds what set_scene would
+// (the scene's bounding sphere) and the emitter's place in Scene::emitters().
+//   point        position | to_world, intensity
+//   spot         to_world, intensity, cutoff_angle (20), beam_width (3/4 cutoff_angle), degrees; a `texture` child is refused
+//   directional  direction | to_world, irradiance
+//   constant     radiance
+class Light : public Emitter {
+public:
+    const mi_light &record() const { return m_rec; }
+protected:
+    void set_value(const Properties &props, const char *name);
+    mi_light m_rec{};
+};
+class PointLight final : public Light { public: explicit PointLight(const Properties &props); };
+class SpotLight final : public Light { public: explicit SpotLight(const Properties &props); };
+class DirectionalEmitter final : public Light { public: explicit DirectionalEmitter(const Properties &props); };
+class ConstantBackgroundEmitter final : public Light { public: explicit ConstantBackgroundEmitter(const Properties &props); };
+// the plugin of that name, or nullptr when `props` names none of the four
+std::shared_ptr<Light> make_light(const Properties &props);
+
 class Mesh {                                                  // include/mitsuba/render/mesh.h
 public:
     Mesh(std::string name, std::vector<float> vertex_positions, std::vector<uint32_t> faces,
@@ -491,6 +512,9 @@ public:
     // an <emitter type="envmap"> child: takes its place in the emitter order after the shapes added
     // so far; "Only one environment emitter can be specified per scene." (scene.cpp:47-50)
     void add_emitter(std::shared_ptr<EnvironmentMapEmitter> env);
+    // an <emitter type="point | spot | directional | constant"> child: like the environment map it takes its place in the
+    // emitter order after the shapes added so far; a constant emitter is an environment emitter (one per scene)
+    void add_emitter(std::shared_ptr<Light> light);
     const EnvironmentMapEmitter *environment() const { return m_env.get(); }   // scene.h:150-151
     // finishes construction: default BSDFs (shape.cpp:75-81), flatten, upload, build accel (scene.cpp:94-97)
     void build(int device = 0, int bvh_quality = 0);   // 0: the binned-SAH tree built on the device (csrc/sah_device.h), 1: by the host recursion
@@ -515,7 +539,7 @@ public:
     std::pair<DirectionSample3f, Spectrum> sample_emitter_direction(const Interaction3f &ref, const std::array<float, 2> &sample,
                                                                      bool test_visibility = true) const;
     float pdf_emitter_direction(const Interaction3f &ref, const DirectionSample3f &ds) const;
-    // Scene::emitters() (scene.h:139-141): area lights and the environment map in the scene's emitter order
+    // Scene::emitters() (scene.h:139-141): area lights, the environment map and the lights in the scene's emitter order
     const std::vector<const Emitter *> &emitters() const { return m_emitter_objs; }
     void ray_intersect_preliminary(const mi_rays_soa &rays, const mi_hits_soa &hits, uint64_t n) const;
     void ray_test(const mi_rays_soa &rays, float *t_out, uint64_t n) const;
@@ -533,6 +557,8 @@ private:
     std::vector<mi_bitmap> m_bitmap_recs; std::vector<std::shared_ptr<BitmapTexture>> m_bitmap_objs;
     std::vector<float> m_bsdf_tables;
     std::shared_ptr<EnvironmentMapEmitter> m_env; size_t m_env_after_shapes = 0; mi_envmap m_env_rec{};
+    struct LightChild { std::shared_ptr<Light> light; size_t after_shapes, seq; };
+    std::vector<LightChild> m_lights; size_t m_env_seq = 0, m_child_seq = 0; std::vector<mi_light> m_light_recs;
     mi_scene_desc m_desc{};
     mi_ctx *m_ctx = nullptr;
     std::vector<mi_ctx *> m_replicas;                          // the contexts of devices[1..] of a multi-GPU build

@@ -499,6 +499,73 @@ AreaLight::AreaLight(const Properties &props) {
     m_radiance_tex = props.texture_record("radiance", 1.f, true, false);
 }
 
+// ---- point / spot / directional / constant ----
+void Light::set_value(const Properties &props, const char *name) {
+    const Color3f v = props.texture(name, 1.f);                // Texture::D65(1) ~ white in RGB mode
+    m_rec.value[0] = v[0]; m_rec.value[1] = v[1]; m_rec.value[2] = v[2];
+    m_rec.value_tex = props.texture_record(name, 1.f, true, false);
+    const Transform4f id;
+    std::memcpy(m_rec.to_world, id.m, 64); std::memcpy(m_rec.to_object, id.inv, 64);
+    m_rec.direction[2] = 1.f;
+}
+static float miw_deg_to_rad(float v) { return v * (float) (M_PI / 180.0); }
+PointLight::PointLight(const Properties &props) {              // point.cpp:49-62
+    m_rec.type = MI_LIGHT_POINT;
+    set_value(props, "intensity");
+    Transform4f tw = props.transform("to_world", Transform4f());
+    if (props.has_property("position")) {
+        if (props.has_property("to_world")) Throw("Only one of the parameters 'position' and 'to_world' can be specified at the same time!'");
+        const Color3f p = props.texture("position");
+        tw = Transform4f::translate({ p[0], p[1], p[2] });
+    }
+    std::memcpy(m_rec.to_world, tw.m, 64); std::memcpy(m_rec.to_object, tw.inv, 64);
+    for (int k = 0; k < 3; ++k) m_rec.position[k] = tw.m[12 + k];
+}
+SpotLight::SpotLight(const Properties &props) {                // spot.cpp:74-97
+    m_rec.type = MI_LIGHT_SPOT;
+    set_value(props, "intensity");
+    if (props.bitmap("intensity")) Throw("The parameter 'intensity' cannot be spatially varying (e.g. bitmap type)!");
+    if (props.has_property("texture")) Throw("spot: a projection 'texture' is not supported");
+    const Transform4f tw = props.transform("to_world", Transform4f());
+    std::memcpy(m_rec.to_world, tw.m, 64); std::memcpy(m_rec.to_object, tw.inv, 64);
+    for (int k = 0; k < 3; ++k) m_rec.position[k] = tw.m[12 + k];
+    float cutoff = props.float_("cutoff_angle", 20.0f);
+    float beam = props.float_("beam_width", cutoff * 3.0f / 4.0f);
+    cutoff = miw_deg_to_rad(cutoff); beam = miw_deg_to_rad(beam);
+    if (!(cutoff >= beam)) Throw("spot: cutoff_angle must not be below beam_width");
+    m_rec.cutoff_angle = cutoff; m_rec.beam_width = beam;
+    m_rec.inv_transition_width = 1.0f / (cutoff - beam);
+    m_rec.cos_cutoff_angle = std::cos(cutoff); m_rec.cos_beam_width = std::cos(beam);
+    m_rec.uv_factor = std::tan(cutoff);
+}
+DirectionalEmitter::DirectionalEmitter(const Properties &props) {   // directional.cpp:49-68
+    m_rec.type = MI_LIGHT_DIRECTIONAL;
+    set_value(props, "irradiance");
+    Transform4f tw = props.transform("to_world", Transform4f());
+    if (props.has_property("direction")) {
+        if (props.has_property("to_world")) Throw("Only one of the parameters 'direction' and 'to_world' can be specified at the same time!'");
+        const Color3f d = props.texture("direction");
+        const miw::V3 dir = miw::normalize(miw::v3(d[0], d[1], d[2]));
+        miw::V3 up, unused;
+        miw::coordinate_system(dir, up, unused);
+        tw = Transform4f::look_at({ 0.f, 0.f, 0.f }, { dir.x, dir.y, dir.z }, { up.x, up.y, up.z });
+    }
+    std::memcpy(m_rec.to_world, tw.m, 64); std::memcpy(m_rec.to_object, tw.inv, 64);
+    for (int k = 0; k < 3; ++k) m_rec.direction[k] = tw.m[8 + k];   // transform_affine(Vector3f(0, 0, 1)), :109
+}
+ConstantBackgroundEmitter::ConstantBackgroundEmitter(const Properties &props) {   // constant.cpp:42-49
+    m_rec.type = MI_LIGHT_CONSTANT;
+    set_value(props, "radiance");
+}
+std::shared_ptr<Light> make_light(const Properties &props) {
+    const std::string &n = props.plugin_name();
+    if (n == "point") return std::make_shared<PointLight>(props);
+    if (n == "spot") return std::make_shared<SpotLight>(props);
+    if (n == "directional") return std::make_shared<DirectionalEmitter>(props);
+    if (n == "constant") return std::make_shared<ConstantBackgroundEmitter>(props);
+    return nullptr;
+}
+
 EnvironmentMapEmitter::EnvironmentMapEmitter(const Properties &props) {
     m_scale = props.float_("scale", 1.f);                      // envmap.cpp:124
     m_to_world = props.transform("to_world", Transform4f());

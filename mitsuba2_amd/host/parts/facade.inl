@@ -164,6 +164,17 @@ void *mih_envmap_create(void *props, uint32_t w, uint32_t h, const float *rgba) 
         return new Box<EnvironmentMapEmitter>{ e }; MIH_CATCH(nullptr)
 }
 void mih_envmap_destroy(void *e) { delete (Box<EnvironmentMapEmitter> *) e; }
+// <emitter type="point | spot | directional | constant">
+void *mih_light_create(void *props) {
+    MIH_TRY
+        const Properties &p = *(Properties *) props;
+        auto l = make_light(p);
+        if (!l) throw std::runtime_error("Plugin \"" + p.plugin_name() + "\" not found!");
+        return new Box<Light>{ l }; MIH_CATCH(nullptr)
+}
+void mih_light_destroy(void *l) { delete (Box<Light> *) l; }
+void mih_light_record(void *l, mi_light *out) { *out = ((Box<Light> *) l)->p->record(); }
+int mih_scene_add_light(void *s, void *l) { MIH_TRY ((Box<Scene> *) s)->p->add_emitter(((Box<Light> *) l)->p); return 0; MIH_CATCH(-1) }
 int mih_scene_add_envmap(void *s, void *e) { MIH_TRY ((Box<Scene> *) s)->p->add_emitter(((Box<EnvironmentMapEmitter> *) e)->p); return 0; MIH_CATCH(-1) }
 // load_xml: `params` = "k1=v1\nk2=v2"; returns handles the caller owns (destroy each with its own mih_*_destroy)
 int mih_load_xml(const char *xml_or_path, int is_file, const char *params, void **scene, void **sensor, void **film, void **sampler, void **integrator) {

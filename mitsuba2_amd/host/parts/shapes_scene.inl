@@ -306,7 +306,17 @@ void Scene::add_shape(std::shared_ptr<Mesh> mesh) {
 void Scene::add_emitter(std::shared_ptr<EnvironmentMapEmitter> env) {
     if (m_built) Throw("Scene: cannot add emitters after build()");
     if (m_env) Throw("Only one environment emitter can be specified per scene.");   // scene.cpp:48-49
-    m_env = std::move(env); m_env_after_shapes = m_shapes.size();
+    for (const LightChild &l : m_lights) if (l.light->record().type == MI_LIGHT_CONSTANT) Throw("Only one environment emitter can be specified per scene.");
+    m_env = std::move(env); m_env_after_shapes = m_shapes.size(); m_env_seq = m_child_seq++;
+}
+void Scene::add_emitter(std::shared_ptr<Light> light) {
+    if (m_built) Throw("Scene: cannot add emitters after build()");
+    if (!light) Throw("Scene: null emitter");
+    if (light->record().type == MI_LIGHT_CONSTANT) {               // scene.cpp:47-50: is_environment()
+        if (m_env) Throw("Only one environment emitter can be specified per scene.");
+        for (const LightChild &l : m_lights) if (l.light->record().type == MI_LIGHT_CONSTANT) Throw("Only one environment emitter can be specified per scene.");
+    }
+    m_lights.push_back({ std::move(light), m_shapes.size(), m_child_seq++ });
 }
 // front and back of a twosided BSDF are the same material (twosided.cpp:72-73)
 static bool miw_same_record(const mi_bsdf &back, const mi_bsdf &front_twosided) {
@@ -477,30 +487,51 @@ void Scene::build(int device, int bvh_quality) {
     m_desc.bsdfs = m_bsdf_recs.data(); m_desc.bsdf_count = (uint32_t) m_bsdf_recs.size();
     m_desc.emitters = m_emitters.data(); m_desc.emitter_count = (uint32_t) m_emitters.size();
     m_desc.envmap = nullptr;
+    // Scene::emitters() (scene.cpp:38-60): the children in declaration order — the area lights with their shapes, the environment map and
+    // the lights where they were added. Every emitter learns its scene and index below.
+    m_emitter_objs.clear();
+    {
+        struct Child { size_t after, seq; const Emitter *e; };
+        std::vector<Child> children;
+        if (m_env) children.push_back({ m_env_after_shapes, m_env_seq, m_env.get() });
+        for (const LightChild &l : m_lights) children.push_back({ l.after_shapes, l.seq, l.light.get() });
+        std::sort(children.begin(), children.end(), [](const Child &a, const Child &b) { return a.after != b.after ? a.after < b.after : a.seq < b.seq; });
+        size_t k = 0;
+        for (size_t i = 0; i <= m_shapes.size(); ++i) {
+            while (k < children.size() && (children[k].after <= i || i == m_shapes.size())) m_emitter_objs.push_back(children[k++].e);
+            if (i < m_shapes.size() && m_shapes[i]->emitter()) m_emitter_objs.push_back(m_shapes[i]->emitter().get());
+        }
+    }
+    auto slot_of = [this](const Emitter *e) { return (uint32_t) (std::find(m_emitter_objs.begin(), m_emitter_objs.end(), e) - m_emitter_objs.begin()); };
+    // scene->bbox().bounding_sphere() (bbox.h:329-332): centre of the bbox, distance to its max corner
+    float bs_center[3], bs_radius;
+    {
+        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+        for (size_t i = 0; i < m_positions.size(); i += 3)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], m_positions[i + a]); hi[a] = std::max(hi[a], m_positions[i + a]); }
+        float d2 = 0.f;
+        for (int a = 0; a < 3; ++a) { bs_center[a] = (lo[a] + hi[a]) * .5f; float d = bs_center[a] - hi[a]; d2 += d * d; }
+        bs_radius = std::sqrt(d2);
+    }
+    m_light_recs.clear();
+    for (const LightChild &l : m_lights) {
+        mi_light r = l.light->record();
+        r.emitter_index = slot_of(l.light.get());
+        std::memcpy(r.bsphere_center, bs_center, 12); r.bsphere_radius = bs_radius;
+        m_light_recs.push_back(r);
+    }
+    m_desc.lights = m_light_recs.empty() ? nullptr : m_light_recs.data(); m_desc.light_count = (uint32_t) m_light_recs.size();
     if (m_env) {
         if (m_env->data().empty()) Throw("envmap: no bitmap set");
         m_env_rec.rgba = m_env->data().data(); m_env_rec.width = m_env->width(); m_env_rec.height = m_env->height();
         m_env_rec.scale = m_env->scale();
         m_env_rec.density = m_env->density().empty() ? nullptr : m_env->density().data();
         std::memcpy(m_env_rec.to_world, m_env->world_transform().m, 64);
-        // emitter order (scene.cpp:38-60): area lights of the shapes added before the envmap come first
-        uint32_t before = 0;
-        for (size_t i = 0; i < m_env_after_shapes && i < m_shapes.size(); ++i) if (m_shapes[i]->emitter()) ++before;
-        m_env_rec.emitter_index = before;
-        // scene->bbox().bounding_sphere() (bbox.h:329-332): centre of the bbox, distance to its max corner
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (size_t i = 0; i < m_positions.size(); i += 3)
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], m_positions[i + a]); hi[a] = std::max(hi[a], m_positions[i + a]); }
-        float c[3], d2 = 0.f;
-        for (int a = 0; a < 3; ++a) { c[a] = (lo[a] + hi[a]) * .5f; float d = c[a] - hi[a]; d2 += d * d; }
-        m_env_rec.bsphere_radius = std::sqrt(d2);
+        m_env_rec.emitter_index = slot_of(m_env.get());        // emitter order: area lights of the shapes added before the envmap come first
+        m_env_rec.bsphere_radius = bs_radius;
         m_desc.envmap = &m_env_rec;
     }
-    // Scene::emitters(): the area lights in shape order with the environment map at its slot; every emitter learns
-    // its scene and index so that Endpoint::eval / sample_direction / pdf_direction can run on the scene's device
-    m_emitter_objs.clear();
-    for (auto &m : m_shapes) if (m->emitter()) m_emitter_objs.push_back(m->emitter().get());
-    if (m_env) m_emitter_objs.insert(m_emitter_objs.begin() + std::min<size_t>(m_env_rec.emitter_index, m_emitter_objs.size()), m_env.get());
+    // every emitter learns its scene and index so that Endpoint::eval / sample_direction / pdf_direction can run on the scene's device
     for (size_t i = 0; i < m_emitter_objs.size(); ++i) {
         Emitter *e = const_cast<Emitter *>(m_emitter_objs[i]);
         // an emitter answers eval / sample_direction / pdf_direction through the ONE scene it is part of (the reference's
@@ -508,6 +539,7 @@ void Scene::build(int device, int bvh_quality) {
         if (e->m_scene && e->m_scene != this)
             Throw("Scene: emitter (or the mesh carrying it) is already part of another scene; build it from its own objects");
         e->m_scene = this; e->m_index = (int32_t) i; e->m_is_env = m_env && e == m_env.get();
+        for (const LightChild &l : m_lights) if (l.light.get() == e && l.light->record().type == MI_LIGHT_CONSTANT) e->m_is_env = true;
     }
     m_built = true;
     if (device < 0) return;                                    // flatten only (host-side tests)

@@ -301,7 +301,13 @@ LoadedScene load_xml_string(const std::string &xml, const std::map<std::string, 
             out.sensor = std::make_shared<PerspectiveCamera>(p, film, sampler);
         } else if (n.tag == "emitter") {
             Properties p(cx.get(n, "type"));
-            if (p.plugin_name() != "envmap") Throw("Error while loading XML: only <emitter type=\"envmap\"> may appear at the top level (area lights belong to a shape)");
+            const std::string &en = p.plugin_name();
+            if (en == "point" || en == "spot" || en == "directional" || en == "constant") {
+                parse_properties(cx, n, p);
+                out.scene->add_emitter(make_light(p));                 // its place among the shapes fixes the emitter order
+                return;
+            }
+            if (en != "envmap") Throw("Error while loading XML: <emitter type=\"" + en + "\"> cannot appear at the top level (envmap, point, spot, directional, constant; area lights belong to a shape)");
             parse_properties(cx, n, p);
             p.set_string("filename", resolve(cx, p.string("filename")));
             out.scene->add_emitter(std::make_shared<EnvironmentMapEmitter>(p));   // its place among the shapes fixes the emitter order

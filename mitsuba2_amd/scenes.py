@@ -324,6 +324,50 @@ def sphere_box(width, height, spp, seed=0, device=0, rfilter="gaussian", **film_
     return scene, cornell_sensor(width, height, spp, seed, rfilter, **film_kw)
 
 
+# One light of each kind for the Cornell geometry (lit_box): the point and the spot hang where the area light is, the
+# directional light and the constant environment reach the room through its open front.
+LIGHT_KINDS = ("point", "spot", "directional", "constant")
+
+
+def make_light(kind, **kw):
+    """-> the api light object of `kind` with the Cornell-sized defaults below; keyword arguments replace them"""
+    if kind == "point":
+        p = dict(position=(278.0, 480.0, 279.5), intensity=(260000.0, 210000.0, 150000.0)); p.update(kw)
+        return api.PointLight(**p)
+    if kind == "spot":
+        p = dict(to_world=dict(origin=(278.0, 540.0, 279.5), target=(278.0, 0.0, 279.5), up=(0, 0, 1)),
+                 intensity=(400000.0, 330000.0, 240000.0), cutoff_angle=50.0, beam_width=30.0); p.update(kw)
+        return api.SpotLight(**p)
+    if kind == "directional":
+        p = dict(direction=(0.25, -0.45, 1.0), irradiance=(3.0, 2.6, 2.0)); p.update(kw)
+        return api.DirectionalEmitter(**p)
+    if kind == "constant":
+        p = dict(radiance=(0.9, 1.0, 1.2)); p.update(kw)
+        return api.ConstantBackgroundEmitter(**p)
+    raise ValueError("make_light: unknown kind %r" % (kind,))
+
+
+def lit_box(kind, width, height, spp, seed=0, device=0, rfilter="gaussian", diffuse_only=True, ball_level=1, bvh_quality=0,
+            light=None, **film_kw):
+    """The Cornell geometry with the area light replaced by one light of `kind` (LIGHT_KINDS). -> (scene, sensor)"""
+    meshes = [m for m in cornell_box_meshes(diffuse_only, ball_level) if m.name != "light"]
+    scene = api.Scene(meshes, lights=[make_light(kind, **(light or {}))]).build(device, bvh_quality)
+    return scene, cornell_sensor(width, height, spp, seed, rfilter, **film_kw)
+
+
+def mixed_light_box(width, height, spp, seed=0, device=0, rfilter="gaussian", diffuse_only=True, ball_level=1, bvh_quality=0, **film_kw):
+    """The Cornell box with its area light, a point light declared before every shape and a constant environment after them: the
+    emitter list is (point, area, constant), so the area light's index shifts and the scene picks among three. -> (scene, sensor)"""
+    point = make_light("point", position=(120.0, 300.0, 150.0), intensity=(90000.0, 110000.0, 130000.0))
+    const = make_light("constant", radiance=(0.5, 0.55, 0.65))
+    meshes = cornell_box_meshes(diffuse_only, ball_level)
+    for i, m in enumerate(meshes):                            # the area light hangs 40 units under the ceiling: shadow rays from the ceiling do not graze it
+        if m.name == "light":
+            meshes[i] = api.Mesh("light", m.vertices - np.array([0, 40.0, 0], np.float32), m.faces, emitter=api.AreaLight(LIGHT_RADIANCE))
+    scene = api.Scene(meshes, lights=[(point, 0), const]).build(device, bvh_quality)
+    return scene, cornell_sensor(width, height, spp, seed, rfilter, **film_kw)
+
+
 def sky_envmap(width=64, height=32, seed=1):
     """Synthetic lat-long HDR sky (the reference's data submodule is absent): vertical sky
     gradient, warm horizon band, dark ground, a sun blob and a little seeded noise. -> H x W x 3 float32."""
