@@ -276,8 +276,12 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
     extern __shared__ uint4 smem[];
     stage_to_lds(sc, cfg, smem);
     const float *thr = stage_thresholds(smem, cfg, UseLog && Q.log_rec ? Q.log_thr : nullptr);
+    // (stage_tables:) the path kernels among the packet kernels also BUILD SceneView::tri_frames / emit_face_n there and read them (scene.h: Frames) — a compile-time property of the
+    // instantiation. Not the direct-integrator kernels: compiled for three wavefronts per SIMD they keep ~40 values in scratch, and with the tables the
+    // MATS_NESTED / MATS_LIGHTS ones keep three more than tests/test_nested_kernel_budget.py / test_lights_kernel_budget.py allow (168 / 164 B per lane for 156 / 152)
+    constexpr bool Frames = MIW_LDS_TABLES && UseLog && Tiny != 0 && Integ != INTEG_DIRECT;
 #if MIW_LDS_TABLES
-    if constexpr (UseLog && Tiny != 0) stage_tables<true, mats_lights(Mats)>(sc, cfg, smem);
+    if constexpr (UseLog && Tiny != 0) stage_tables<true, mats_lights(Mats), mats_full(Mats), Frames>(sc, cfg, smem);
 #endif
 #if defined(MIW_SECTION_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
     if ((threadIdx.x & 63u) == 0) { unsigned long long *b_ = miw_sec_buf(); for (int i = 0; i < 15; ++i) b_[i] = 0; b_[15] = __builtin_amdgcn_s_memtime(); }
@@ -307,7 +311,7 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
         __shared__ uint32_t s_prog[MIW_BLOCK / 64];
         if (cfg.tail_prio) work.enable_tail_prio(sample_end, &s_prog[threadIdx.x >> 6]);
         if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<Mats, Analytic>(P, sc, sample_end, work, tr2, &local);
-        else pixel_stream_render<Mats, Analytic>(P, sc, sample_end, work, tr2, &local);
+        else pixel_stream_render<Mats, Analytic, Frames>(P, sc, sample_end, work, tr2, &local);
     } else if (lane < P.n_lanes) {
         U4 st = Q.st[lane];
         if (!(st.z & LF_DONE)) {

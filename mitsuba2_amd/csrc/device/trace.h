@@ -19,7 +19,8 @@ struct TraceLds {           // what a trace workgroup finds in its dynamic LDS
     uint32_t tail_prio;     // 1: least-progress-first wave priorities (QueueWork::tick) — shards of about one pixel per resident lane
     uint32_t thr16;         // render kernels that log 16-byte records: uint4 offset of the 256 phase thresholds (film.h) in dynamic LDS
     uint32_t tab16;         // packet kernels and the phase machine: uint4 offset of the scene's small tables in dynamic LDS (stage_tables)
-    uint32_t tab_words[10]; // dwords of: shapes, bsdfs, emitters, emit_tri, emit_vnorm, emit_pmf, emit_cdf; packet kernels also: tris, tri_vn, tri_uv (0: absent)
+    uint32_t tab_words[12]; // dwords of: shapes, bsdfs, emitters, emit_tri, emit_vnorm, emit_pmf, emit_cdf; packet kernels also: tris, tri_vn, tri_uv (0: absent),
+                            // and of the two tables they BUILD behind those: tri_frames (12 per triangle), emit_face_n (4 per emitter face)
     uint32_t env_top_count, env_top_base, env_top_words;   // the environment warp's top levels behind the tables (envmap.h: EnvTop); 0: none
     uint32_t pool_claim_min; // k_path_pooled: a walk loop looks for new jobs only when this many lanes of a slot are empty
     uint32_t pool16, stat16; // k_path_pooled (pooled_kernel.h): uint4 offsets of the workgroup's walk-job records (5 x 16 B per lane) and of their status bytes
@@ -110,7 +111,13 @@ __device__ __forceinline__ const float *stage_thresholds(uint4 *smem, TraceLds c
 // kernels that call it (the pointers must not be a choice between address spaces): the host launches those kernels only when
 // the tables fit (mi_render / mi_bvh_build), the lock-step tree kernels read the tables from global memory as before.
 // Lights (the MATS_LIGHTS kernels): the light table follows the other tables, and SceneView::lights / constant point at the copy.
-template <bool WithTris, bool Lights = false>     // packet scenes (<= 64 triangles): the triangle records the shading reads, their vertex normals and texture coordinates too
+// WithTris also BUILDS two tables behind the copies (round 7): the TriFrame of every triangle (shape.h: the half of compute_surface_interaction that
+// is a function of the triangle alone — normal, tangent, the frame of a face without vertex normals) and the normal of every emitter face
+// (mesh_sample_position). One lane per record, once per workgroup of a grid sized to the machine, by the same functions the per-hit code would
+// call — same compiler, same flags, same values. Texcoords: whether the kernel's hit_surface_interaction reads texture coordinates (scene.h); the
+// frames are built from exactly what it would pass. SceneView::tri_frames / emit_face_n point at them; code compiled with Frames = true reads them.
+// BuildFrames = false: neither table is built (their LDS, which the host reserves for every packet launch, stays unused) and the pointers stay nullptr.
+template <bool WithTris, bool Lights = false, bool Texcoords = false, bool BuildFrames = false>     // packet scenes (<= 64 triangles): the triangle records the shading reads, their vertex normals and texture coordinates too
 __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg, uint4 *smem) {
     constexpr int N = WithTris ? 10 : 7;
     uint32_t *dst = reinterpret_cast<uint32_t *>(smem + cfg.tab16);
@@ -126,6 +133,27 @@ __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg,
         at[k] = dst + off;
         for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[off + i] = src[k][i];
         off += (n + 3u) & ~3u;                                  // every table starts on a 16-byte boundary
+    }
+    TriFrame *frames_at = reinterpret_cast<TriFrame *>(dst + off);
+    if constexpr (WithTris && BuildFrames) {
+        // (from the records in global memory: the copies above are not visible before the barrier below)
+        const uint32_t n_frames = cfg.tab_words[10] / (uint32_t) (sizeof(TriFrame) / 4);     // = sc.tri_count
+        for (uint32_t i = threadIdx.x; i < n_frames; i += blockDim.x) {
+            const Tri &tr = sc.tris[i];
+            const float *tc = (Texcoords && (sc.shapes[tr.shape].flags & SHAPE_HAS_TEXCOORDS)) ? sc.tri_uv + 6 * (size_t) tr.prim : nullptr;
+            frames_at[i] = tri_frame(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), tc);
+        }
+        off += (cfg.tab_words[10] + 3u) & ~3u;
+    }
+    float *face_n_at = reinterpret_cast<float *>(dst + off);
+    if constexpr (WithTris && BuildFrames) {
+        const uint32_t n_faces = cfg.tab_words[11] / 4u;                                     // = faces of emit_tri
+        for (uint32_t f = threadIdx.x; f < n_faces; f += blockDim.x) {
+            const float *p = sc.emit_tri + 9 * (size_t) f;
+            const V3 n = face_normal(ld3(p), ld3(p + 3), ld3(p + 6));
+            face_n_at[4 * f] = n.x; face_n_at[4 * f + 1] = n.y; face_n_at[4 * f + 2] = n.z; face_n_at[4 * f + 3] = 0.f;
+        }
+        off += cfg.tab_words[11];
     }
     uint32_t *lights_at = dst + off;
     if constexpr (Lights) {
@@ -154,6 +182,7 @@ __device__ __forceinline__ void stage_tables(SceneView &sc, const TraceLds &cfg,
     }
     if (WithTris) {                                                  // (tri_vn / tri_uv: read only for shapes whose flags say so)
         sc.tris = reinterpret_cast<const Tri *>(at[7]); sc.tri_vn = reinterpret_cast<const float *>(at[8]); sc.tri_uv = reinterpret_cast<const float *>(at[9]);
+        if constexpr (BuildFrames) { sc.tri_frames = frames_at; sc.emit_face_n = face_n_at; }
     }
 }
 

@@ -322,7 +322,9 @@ MIW_HD constexpr bool mats_full(int mats) { return mats == MATS_ALL || mats == M
 MIW_HD constexpr bool mats_nested(int mats) { return mats == MATS_NESTED || mats == MATS_LIGHTS; }   // wrapper resolution, null / thindielectric
 MIW_HD constexpr bool mats_lights(int mats) { return mats == MATS_LIGHTS; }
 // `Analytic` = false compiles the analytic-shape branch out (scenes the caller knows to be triangles only).
-template <int Mats = MATS_ALL, bool Analytic = true, typename PrevO, typename Cnt>
+// `Frames` = true: the caller built SceneView::tri_frames / emit_face_n (the packet kernels; scene.h) — the per-triangle constants of
+// the interaction and of the emitter sample are read from them instead of being recomputed per segment.
+template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, typename PrevO, typename Cnt>
 MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4 h, PrevO prev_o,
                      ShadowOut &sh, Cnt *cnt_local) {
     sh.has = false;
@@ -335,7 +337,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     uint32_t bsdf_index = 0;
     int32_t emitter = -1;                            // scene.h:243-253 (no environment emitter)
     // only MATS_ALL kernels are launched for scenes with texture coordinates (miwave.hip: diffuse_only / textured)
-    if (valid) hit_surface_interaction<Analytic, mats_full(Mats)>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
+    if (valid) hit_surface_interaction<Analytic, mats_full(Mats), Frames>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
     else emitter = miss_emitter<mats_lights(Mats)>(sc);   // a miss sees the environment, scene.h:248-249
     if (depth == 1 && valid) L.flags |= LF_VALID_RAY;   // path.cpp:121
     MIW_SECTION(7);                                   // (sections 6.. : the shade body of the phase machine, debug builds)
@@ -393,7 +395,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     // ---- emitter sampling, :155-172 ----
     if (bflags & BSDF_Smooth) {
         DirectionSample ds;
-        Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats)>(sc, si.p, next_2d(L.rng), ds, L.wl);
+        Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats), Frames>(sc, si.p, next_2d(L.rng), ds, L.wl);
         if (ds.pdf != 0.f) {
             V3 wo = to_local(si.sh, ds.d);
             Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_eval(*bsdf.b, si.wi, wo, tc) : bsdf_side_eval<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
@@ -503,7 +505,7 @@ MIW_HD uint32_t lane_shade(const RenderParams &P, const SceneView &sc, const Lan
 // store(st) publishes a pixel's state when its run is over, put(...) is block->put(). A lane that
 // finishes a pixel fetches the next one INSIDE the iteration loop, so the other lanes of its wavefront
 // never wait for it (the device feeds lanes from one shared queue; the CPU checker hands out one pixel).
-template <int Mats = MATS_ALL, bool Analytic = true, typename Work, typename Trace2, typename Cnt>
+template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, typename Work, typename Trace2, typename Cnt>
 MIW_HD void pixel_stream_render(const RenderParams &P, const SceneView &sc, uint32_t sample_end, Work &work,
                                 Trace2 trace2, Cnt *cnt_local) {
     LaneRegs L;
@@ -537,7 +539,7 @@ MIW_HD void pixel_stream_render(const RenderParams &P, const SceneView &sc, uint
         sh.has = false;
         int r = STEP_FINISHED;
         if (!dead_pending) {
-            r = path_step<Mats, Analytic>(P, sc, L, h, [o]() { return o; }, sh, cnt_local);
+            r = path_step<Mats, Analytic, Frames>(P, sc, L, h, [o]() { return o; }, sh, cnt_local);
             MIW_SECTION(4);
             if (r == STEP_DEAD_PENDING) { dead_pending = true; continue; }   // one more pass for its shadow ray
             if (r == STEP_CONTINUE) continue;

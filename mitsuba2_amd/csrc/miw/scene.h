@@ -70,6 +70,9 @@ struct SceneView {
     const struct Bvh4Node *nodes4;                  // device only: the 4-wide quantised tree the phase machine walks (bvh4.h) or nullptr
     const struct Bvh8Node *nodes8;                  // device only: the 8-wide quantised tree (bvh8.h) of a view whose tris / tri_vn are in that tree's order, or nullptr
     const float *env_top; uint32_t env_top_count, env_top_base;   // device only: the environment warp's top levels in LDS (envmap.h: EnvTop); count 0: none
+    const TriFrame *tri_frames;                     // device only: TriFrame per triangle (leaf order), built in LDS by the packet kernels (trace.h: stage_tables); nullptr elsewhere
+    const float *emit_face_n;                       // device only: face_normal() of every emitter face, 4 floats each, beside it; nullptr elsewhere. Both are read
+                                                    // only by code compiled with Frames = true (below): the kernels that built them
     const LightRec *lights;                         // point / spot / directional / constant emitters (EmitterRec::tri_first indexes this table) or nullptr;
     const LightRec *constant;                       // the constant environment emitter among them or nullptr: what a miss sees in a scene without envmap.
                                                     // Read only by code compiled with Lights = true (below); the classes of scenes without lights never touch either
@@ -87,7 +90,9 @@ MIW_HD PrimCtx prim_ctx(const SceneView &sc) { PrimCtx c; c.rects = sc.rects; c.
 // (ray_o(), ray_d), plus the two lookups the integrators make on it: si.bsdf() (bsdf.h:485-500) and si.emitter()
 // (scene.h:243-253). Analytic = false / Texcoords = false compile the analytic-shape branch / the texture-coordinate
 // path out (scenes the caller knows to have none). One definition for the path kernels and for mi_ray_intersect.
-template <bool Analytic, bool Texcoords, typename RayO>
+// Frames = true (the packet kernels, which built SceneView::tri_frames): the per-triangle half of compute_surface_interaction
+// comes from that table (shape.h: TriFrame).
+template <bool Analytic, bool Texcoords, bool Frames = false, typename RayO>
 MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float t, float u, float v, RayO ray_o, V3 ray_d,
                                     SurfaceInteraction &si, uint32_t &bsdf_index, int32_t &emitter) {
     const Tri &tr = sc.tris[tri_idx];
@@ -99,7 +104,8 @@ MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float
     } else {
         const float *vn = (shape.flags & 1u) ? sc.tri_vn + 9 * (size_t) tri_idx : nullptr;
         const float *tc = (Texcoords && (shape.flags & SHAPE_HAS_TEXCOORDS)) ? sc.tri_uv + 6 * (size_t) tr.prim : nullptr;
-        compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, t, u, v, ray_d, si);
+        if constexpr (Frames) compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, sc.tri_frames[tri_idx], t, u, v, ray_d, si);
+        else compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, t, u, v, ray_d, si);
     }
     si.shape = tr.shape; si.prim = tr.prim;
     emitter = shape.emitter; bsdf_index = shape.bsdf;
@@ -243,7 +249,8 @@ MIW_HD Spec env_eval_spec(const EnvmapRec &e, V3 d, const Wavelengths &) { retur
 // shape.cpp:292-309) or the environment map (envmap.cpp:157-190). Returns radiance / pdf; `ds.pdf == 0`: no sample.
 // Analytic = false: the caller knows the scene to hold no analytic shapes, hence no sphere / rectangle lights (their code is compiled out).
 // Lights = true: the table may hold point / spot / directional / constant records (light.h); false compiles them out.
-template <bool Analytic = true, bool Lights = false>
+// Frames = true: the normal of a sampled mesh face comes from SceneView::emit_face_n (the packet kernels).
+template <bool Analytic = true, bool Lights = false, bool Frames = false>
 MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     const EmitterRec &e = sc.emitters[index];
     Spec value;
@@ -260,8 +267,10 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
             sphere_sample_direction(sc.rects[e.tri_first], ref_p, sample, ds);      // the sphere's own sample_direction
         } else {
             // Shape::sample_direction, shape.cpp:292-309
-            PositionSample ps = (Analytic && (e.flags & 2u)) ? rect_sample_position(sc.rects[e.tri_first], sample)
-                                                             : mesh_sample_position(emitter_mesh(sc, e), sample);
+            PositionSample ps;
+            if (Analytic && (e.flags & 2u)) ps = rect_sample_position(sc.rects[e.tri_first], sample);
+            else if constexpr (Frames) ps = mesh_sample_position(emitter_mesh(sc, e), sample, FaceNormalTable{ sc.emit_face_n + 4 * (size_t) e.tri_first });
+            else ps = mesh_sample_position(emitter_mesh(sc, e), sample);
             ds.p = ps.p; ds.n = ps.n; ds.pdf = ps.pdf;
             ds.d = ds.p - ref_p;
             float dist_squared = squared_norm(ds.d);
@@ -281,7 +290,7 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
 // scene.cpp:164-200, *without* the visibility test (the shadow ray is a separate stage of the kernels;
 // mi_sample_emitter_direction traces it on request). Returns the unoccluded emitter value; `ds.pdf == 0`
 // means "no sample" (path.cpp:160).
-template <bool Analytic = true, bool Lights = false>
+template <bool Analytic = true, bool Lights = false, bool Frames = false>
 MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     if (sc.emitter_count == 0) {                       // scene.cpp:208-211
         ds.p = ds.n = ds.d = v3(0.f); ds.dist = 0.f; ds.pdf = 0.f; ds.emitter = 0;
@@ -297,7 +306,7 @@ MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, D
         index = i < sc.emitter_count - 1 ? i : sc.emitter_count - 1;
         sample.x = (sample.x - (float) index * emitter_pdf) * n;
     }
-    Spec value = emitter_sample_direction<Analytic, Lights>(sc, index, ref_p, sample, ds, wl);
+    Spec value = emitter_sample_direction<Analytic, Lights, Frames>(sc, index, ref_p, sample, ds, wl);
     if (sc.emitter_count > 1) {                        // scene.cpp:195-197
         ds.pdf *= emitter_pdf;
         value = value * rcp(emitter_pdf);

@@ -185,6 +185,68 @@ struct SurfaceInteraction {
 // `vn` = per-vertex normals of this face or nullptr (mesh.cpp:514-519);
 // `tc` = per-vertex texture coordinates of this face (u0 v0 u1 v1 u2 v2) or nullptr (:492-511): they replace the
 // barycentric uv and, where the uv parameterisation is not degenerate, the tangents the shading frame is built on.
+//
+// What of it is a function of the triangle alone (and of its texture coordinates), not of the hit: the geometric normal, the
+// tangent dp_du and — for a face without vertex normals, whose shading normal IS the geometric one — the whole shading frame.
+// tri_frame() holds those statements, compute_surface_interaction(..., frame, ...) the per-hit rest; the classic signatures
+// are the one followed by the other in one body (below), so every caller runs the same operations on the same values. The
+// packet kernels build the records once per workgroup (device/trace.h: stage_tables) and call the second half alone.
+struct TriFrame { float n[3], dp_du[3], s[3], t[3]; };       // 48 B = 3 x b128; s, t: the frame of sh.n = n
+MIW_HD void st3(float *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+MIW_HD TriFrame tri_frame(V3 p0, V3 p1, V3 p2, const float *tc) {
+    V3 dp0 = p1 - p0, dp1 = p2 - p0;
+    const V3 n = normalize(cross(dp0, dp1));           // mesh.cpp:487
+    V3 dp_du, dp_dv;
+    coordinate_system(n, dp_du, dp_dv);                // :491
+    if (tc) {                                          // :492-511
+        const V2 uv0 = v2(tc[0], tc[1]), uv1 = v2(tc[2], tc[3]), uv2 = v2(tc[4], tc[5]);
+        const V2 duv0 = v2(uv1.x - uv0.x, uv1.y - uv0.y), duv1 = v2(uv2.x - uv0.x, uv2.y - uv0.y);
+        const float det = fmsub(duv0.x, duv1.y, duv0.y * duv1.x), inv_det = rcp(det);             // :503-504
+        if (det != 0.f) {                                                                          // :506-509
+            dp_du = fmsub3(dp0, duv1.y, dp1 * duv0.y) * inv_det;
+            dp_dv = fnmadd3(dp0, duv1.x, dp1 * duv0.x) * inv_det;
+        }
+    }
+    (void) dp_dv;
+    // initialize_sh_frame, interaction.h:153-156, of sh.n = n (mesh.cpp:541)
+    const V3 s = normalize(fnmadd3(n, dot(n, dp_du), dp_du));
+    const V3 t = cross(n, s);
+    TriFrame f;
+    st3(f.n, n); st3(f.dp_du, dp_du); st3(f.s, s); st3(f.t, t);
+    return f;
+}
+// The per-hit half: `frame` = tri_frame(p0, p1, p2, tc) of the same triangle and the same `tc`.
+MIW_HD void compute_surface_interaction(V3 p0, V3 p1, V3 p2, const float *vn, const float *tc, const TriFrame &frame,
+                                        float t, float b1, float b2, V3 ray_d,
+                                        SurfaceInteraction &si) {
+    float b0 = 1.f - b1 - b2;
+    si.t = t;
+    si.p = p0 * b0 + p1 * b1 + p2 * b2;                // mesh.cpp:484
+    si.n = ld3(frame.n);                               // :487
+    si.uv = v2(b1, b2);                                // :490
+    if (tc) {
+        const V2 uv0 = v2(tc[0], tc[1]), uv1 = v2(tc[2], tc[3]), uv2 = v2(tc[4], tc[5]);
+        si.uv = v2(uv0.x * b0 + uv1.x * b1 + uv2.x * b2, uv0.y * b0 + uv1.y * b1 + uv2.y * b2);   // :497
+    }
+    if (vn) {                                          // :514-519
+        V3 n0 = ld3(vn), n1 = ld3(vn + 3), n2 = ld3(vn + 6);
+        const V3 dp_du = ld3(frame.dp_du);
+        si.sh.n = normalize(n0 * b0 + n1 * b1 + n2 * b2);
+        // initialize_sh_frame, interaction.h:153-156
+        si.sh.s = normalize(fnmadd3(si.sh.n, dot(si.sh.n, dp_du), dp_du));
+        si.sh.t = cross(si.sh.n, si.sh.s);
+    } else {
+        si.sh.n = si.n;                                // :541
+        si.sh.s = ld3(frame.s);
+        si.sh.t = ld3(frame.t);
+    }
+    si.wi = to_local(si.sh, -ray_d);                   // interaction.h:591
+}
+// The classic form: both halves in one body, statement for statement what tri_frame() and the overload above do one after the
+// other (tools/tri_frames_check.cpp pins the three against each other bit for bit). It stays ONE body — the shading normal selected
+// first, one copy of the frame code behind the selection — because the register budgets of the tree and sample kernels are pinned
+// to the code this form compiles to (tests/test_*_kernel_budget.py): composed of the two calls, a smooth shape's frame code is a second
+// copy in its own branch, and k_sample_rays<tree, MATS_LIGHTS, direct> keeps two more values in scratch.
 MIW_HD void compute_surface_interaction(V3 p0, V3 p1, V3 p2, const float *vn, const float *tc,
                                         float t, float b1, float b2, V3 ray_d,
                                         SurfaceInteraction &si) {
@@ -296,8 +358,14 @@ MIW_HD PositionSample rect_sample_position(const AnalyticRec &r, V2 sample) {
     return ps;
 }
 
-// mesh.cpp:352-397
-MIW_HD PositionSample mesh_sample_position(const MeshSampler &m, V2 sample) {
+// mesh.cpp:352-397. `face_n(idx, e0, e1)` = the geometric normal of face `idx`, read only for a mesh without vertex
+// normals: computed on the spot (FaceNormalCompute: the classic form below), or looked up in a table of face_normal()
+// records, 4 floats per face of this mesh (FaceNormalTable: the packet kernels, device/trace.h: stage_tables).
+MIW_HD V3 face_normal(V3 p0, V3 p1, V3 p2) { return normalize(cross(p1 - p0, p2 - p0)); }
+struct FaceNormalCompute { MIW_HD V3 operator()(uint32_t, V3 e0, V3 e1) const { return normalize(cross(e0, e1)); } };
+struct FaceNormalTable { const float *n; MIW_HD V3 operator()(uint32_t idx, V3, V3) const { return ld3(n + 4 * (size_t) idx); } };
+template <typename FaceN>
+MIW_HD PositionSample mesh_sample_position(const MeshSampler &m, V2 sample, FaceN face_n) {
     // sample_reuse, distr_1d.h:193-203
     uint32_t idx = distr_sample(m, sample.y);
     float pmf = m.pmf[idx] * m.normalization,
@@ -318,9 +386,12 @@ MIW_HD PositionSample mesh_sample_position(const MeshSampler &m, V2 sample) {
         V3 n0 = ld3(vn), n1 = ld3(vn + 3), n2 = ld3(vn + 6);
         ps.n = normalize(n0 * (1.f - b.x - b.y) + n1 * b.x + n2 * b.y);
     } else {
-        ps.n = normalize(cross(e0, e1));
+        ps.n = face_n(idx, e0, e1);
     }
     return ps;
+}
+MIW_HD PositionSample mesh_sample_position(const MeshSampler &m, V2 sample) {
+    return mesh_sample_position(m, sample, FaceNormalCompute{});
 }
 
 // mesh.h:107-117

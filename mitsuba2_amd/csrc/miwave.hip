@@ -707,18 +707,22 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
 // ---- BVH build ------------------------------------------------------------------------
 // dwords of the tables stage_tables() copies into LDS (shapes, bsdfs, emitters, emit_tri, emit_vnorm, emit_pmf, emit_cdf), each
 // padded to 16 bytes; returns the bytes of the block
-#define MIW_LDS_PER_WORKGROUP (40u * 1024u)       /* 160 KB per CU / four workgroups of 256 (four wavefronts per SIMD) */
-#define MIW_LDS_STATIC 1024u                      /* static __shared__ of k_path_phased: s_job_pend (QueueWork: a word per lane); s_prog, 16 bytes, inside the granule below */
+#define MIW_LDS_PER_CU (160u * 1024u)
+#define MIW_LDS_PER_WORKGROUP (MIW_LDS_PER_CU / 4u) /* 160 KB per CU / four workgroups of 256 (four wavefronts per SIMD) */
+#define MIW_LDS_STATIC 1024u                      /* static __shared__ of k_path_phased and of the packet kernels: s_job_pend (QueueWork: a word per lane); s_prog, 16 bytes, inside the granule below */
 #define MIW_LDS_GRANULE 512u                      /* LDS is handed out in granules: dynamic + static, rounded up, must stay inside 40 KB */
-static size_t lds_table_bytes(const mi_ctx *c, uint32_t words[10], bool with_tris) {
+static size_t lds_table_bytes(const mi_ctx *c, uint32_t words[12], bool with_tris) {
     words[0] = (uint32_t) (c->shapes.size() * sizeof(ShapeRec) / 4); words[1] = (uint32_t) (c->bsdfs.size() * sizeof(BsdfRec) / 4);
     words[2] = (uint32_t) (c->emitters.size() * sizeof(EmitterRec) / 4);
     words[3] = (uint32_t) c->emit_tri.size(); words[4] = (uint32_t) c->emit_vnorm.size(); words[5] = (uint32_t) c->emit_pmf.size(); words[6] = (uint32_t) c->emit_cdf.size();
     // packet scenes: the triangle records (leaf order), their vertex normals and per-face texture coordinates as well
     words[7] = with_tris ? (uint32_t) (c->tris_in.size() * sizeof(Tri) / 4) : 0u;
     words[8] = with_tris ? (uint32_t) c->tri_vn_in.size() : 0u; words[9] = with_tris ? (uint32_t) c->tri_uv_in.size() : 0u;
+    // ... and the two tables the packet kernels build behind them (trace.h: stage_tables): a TriFrame per triangle, a normal (16 B) per emitter face
+    words[10] = with_tris ? (uint32_t) (c->tris_in.size() * sizeof(TriFrame) / 4) : 0u;
+    words[11] = with_tris ? (uint32_t) (c->emit_tri.size() / 9 * 4) : 0u;
     size_t total = 0;
-    for (int k = 0; k < 10; ++k) total += ((size_t) words[k] + 3u) / 4u * 16u;
+    for (int k = 0; k < 12; ++k) total += ((size_t) words[k] + 3u) / 4u * 16u;
     total += c->lights.size() * sizeof(LightRec);             // the light table behind them (TraceLds::light_words; sizeof(LightRec) is a multiple of 16)
     return total;
 }
@@ -746,7 +750,7 @@ mi_status mi_bvh_build(mi_ctx *c, int32_t quality) {
     int max_fan = 4;
     if (const char *e = c->opt.get("MIW_BVH4_FAN")) max_fan = std::min(4, std::max(2, atoi(e)));
     double ms_bvh4 = 0.0;
-    uint32_t tab_words_[10];
+    uint32_t tab_words_[12];
     // (the packet kernels read the scene's small tables from LDS: a scene of <= 64 triangles whose tables would not fit beside the
     // packets — dozens of unused BSDF records — is walked as a tree instead)
     const bool tiny = c->tris_in.size() <= MIW_BRUTE_MAX_TRIS && !force_tree && c->rects.empty() &&   // packets are triangles only
@@ -1004,6 +1008,7 @@ mi_status mi_bvh_build(mi_ctx *c, int32_t quality) {
     v.lights = c->lights.empty() ? nullptr : c->d_lights.p;
     v.constant = c->constant_light >= 0 ? c->d_lights.p + c->constant_light : nullptr;
     v.env_top = nullptr; v.env_top_count = v.env_top_base = 0;      // (set inside the kernels that stage them: trace.h stage_tables)
+    v.tri_frames = nullptr; v.emit_face_n = nullptr;                // (built in LDS by the packet kernels that read them: trace.h stage_tables)
     v.rects = c->rects.empty() ? nullptr : c->d_rects.p; v.rect_count = (uint32_t) c->rects.size();
 
     // LDS plan: whole scene if it fits in 16 KiB (keeps 8 workgroups/CU resident),
@@ -1964,8 +1969,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         L.table_bytes = lds_table_bytes(c, L.cfg.tab_words, c->lds_cfg.brute != 0);
         L.cfg.light_words = (uint32_t) (c->lights.size() * sizeof(LightRec) / 4);
         // (packet scenes always stage: mi_bvh_build bounded their tables by 24 KB, which with the packets, boxes and thresholds stays
-        // inside the 64 KB a workgroup may ask for — at fewer workgroups per CU past 40 KB)
-        L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u : lds_budget);
+        // inside the 64 KB a workgroup may ask for, less the kernels' static __shared__ and a granule — at fewer workgroups per CU past
+        // what lds_workgroups() below allows)
+        L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u - MIW_LDS_STATIC - MIW_LDS_GRANULE : lds_budget);
         L.cfg.env_top_count = L.cfg.env_top_base = L.cfg.env_top_words = 0;
         if (L.tables_fit && c->have_env && !(ropt.get("MIW_ENV_TOP") && atoi(ropt.get("MIW_ENV_TOP")) == 0)) {
             // ... and as many of the environment warp's smallest levels as fit what is left (at most env_cap): levels are stored from
@@ -2021,8 +2027,15 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                                          pool_nw, pool_pp, layp.rlds, (size_t) pool16 * 16, 5u * NJ * 16u, layp.table_bytes, layp.cfg.env_top_words * 4u, (int) pooled_fits);
     }
     TraceLds rcfg = lay.cfg; size_t rlds = lay.rlds; const size_t rlds_plain = lay.rlds_plain, table_bytes = lay.table_bytes; const bool tables_fit = lay.tables_fit;
-    if (ropt.get("MIW_DEBUG")) fprintf(stderr, "[miwave] LDS per workgroup: %zu bytes dynamic with the scene tables (%zu without), tables %zu B of which environment warp levels %u B, budget %zu%s\n",
-                                     rlds, rlds_plain, table_bytes, rcfg.env_top_words * 4u, lds_budget4, stack8_sized ? "; stack sized for the 8-wide tree's depth" : "");
+    if (MIW_LDS_TABLES && c->lds_cfg.brute && !tables_fit) return fail(c, MI_ERR_STATE, "render: the tables of this packet scene do not fit a workgroup's LDS");
+    // workgroups of a kernel with `dyn` bytes of dynamic LDS (+ its static __shared__, in granules) that one CU holds
+    auto lds_workgroups = [](size_t dyn) -> uint32_t {
+        const size_t per = (dyn + MIW_LDS_STATIC + 16u + MIW_LDS_GRANULE - 1u) / MIW_LDS_GRANULE * MIW_LDS_GRANULE;
+        return (uint32_t) (MIW_LDS_PER_CU / per);
+    };
+    if (ropt.get("MIW_DEBUG")) fprintf(stderr, "[miwave] LDS per workgroup: %zu bytes dynamic with the scene tables (%zu without), tables %zu B of which environment warp levels %u B and built frame tables %u B, budget %zu%s; + %u static: %u workgroups per CU by LDS\n",
+                                     rlds, rlds_plain, table_bytes, rcfg.env_top_words * 4u, (rcfg.tab_words[10] + rcfg.tab_words[11]) * 4u, lds_budget4, stack8_sized ? "; stack sized for the 8-wide tree's depth" : "",
+                                     MIW_LDS_STATIC + 16u, lds_workgroups(rlds));
 
     mi_counters &K = c->counters;
     K.samples = K.segments = K.shadow_rays = K.iterations = 0; K.lanes = n_lanes;
@@ -2091,7 +2104,10 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // 128-register instantiation for four: resident_kernel.h; MIW_PACKET_SHARD4=0 keeps five)
         bool packet_shard4 = !phased && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct && c->view.tri_count <= 32u && MIW_PACKET_WAVES > 4 && film_mode == 1 && n_lanes <= 64u * 4u * n_simd;
         if (const char *e = ropt.get("MIW_PACKET_SHARD4")) packet_shard4 = packet_shard4 && atoi(e) != 0;
-        const uint32_t res_waves = phased ? (uint32_t) ph_waves : !tiny ? (uint32_t) MIW_TREE_WAVES : (c->diffuse_only && !MIW_SPECTRAL ? (c->view.tri_count <= 32u && !packet_shard4 ? (uint32_t) MIW_PACKET_WAVES : 4u) : (uint32_t) MIW_PACKET_WAVES_ALL);
+        const uint32_t res_waves_compiled = phased ? (uint32_t) ph_waves : !tiny ? (uint32_t) MIW_TREE_WAVES : (c->diffuse_only && !MIW_SPECTRAL ? (c->view.tri_count <= 32u && !packet_shard4 ? (uint32_t) MIW_PACKET_WAVES : 4u) : (uint32_t) MIW_PACKET_WAVES_ALL);
+        // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
+        // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
+        const uint32_t res_waves = tiny && film_mode == 1 ? std::max(1u, std::min(res_waves_compiled, lds_workgroups(rlds))) : res_waves_compiled;
         bool place = film_mode == 1 && !direct && (tiny || phased_placeable) && n_lanes >= 64u * n_simd / 2u && n_lanes <= 64u * res_waves * n_simd &&
                      cfg->spp >= 128u && per_launch >= cfg->spp && cfg->timeout_s <= 0.f;
         if (const char *e = ropt.get("MIW_PLACE")) place = place && atoi(e) != 0;
