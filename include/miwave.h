@@ -481,6 +481,37 @@ mi_status mi_sample(mi_ctx *ctx, const mi_sample_cfg *cfg, const mi_rays_soa *ra
  * Returns MI_ERR_CANCELLED if mi_cancel()/timeout stopped it (film holds the
  * partial result, like the reference's `return !m_stop`). */
 mi_status mi_render(mi_ctx *ctx, const mi_render_cfg *cfg, void *film);
+/* The aov integrator (src/integrators/aov.cpp): SamplingIntegrator::render with G-buffer channels beside an optional nested
+ * integrator. The film has mi_aov_channel_count(aov) = 5 + N float32 channels per texel: X Y Z A W, then the channels of `types`
+ * in their order (aov.cpp:83-131), then — with a child — its .R .G .B .A (aov.cpp:137-150).
+ *   types    depth: si.t (1 channel); position: si.p; uv: si.uv (2); geo_normal: si.n; sh_normal: si.sh_frame.n; dp_du, dp_dv (3
+ *            each); duv_dx, duv_dy (2 each: always 0 — interaction.h:593 clears them and aov.cpp never fills them). A sample whose
+ *            ray hits nothing contributes 0 to every one of them, depth included (aov.cpp:167).
+ *   nested   MI_AOV_NESTED_NONE: X = Y = Z = A = 0, W = 1 per sample (aov.cpp:164). _PATH / _DIRECT (the scalar_rgb library): `child`
+ *            describes it as for mi_sample (on_device is ignored); it receives the ray and the sampler of every camera sample, so
+ *            channels 0 .. 4 are the film mi_render renders for that integrator.
+ * Of `cfg` the camera, film, filter, block, seed, spp, samples_per_launch (> 0: that many samples of every pixel per launch;
+ * else the frame in one launch — a frame with a child always advances one sample per round of launches), accumulate,
+ * film_on_device, timeout_s and profile (times into mi_counters: ms_path = the sample launches, ms_film_blocks, ms_film_merge,
+ * ms_render) fields apply; integrator, max_depth, rr_depth and the direct / moment / plan / debug fields do
+ * not. A frame is rendered by one context: a tile shard (cfg->tile_list != NULL) is refused, and so are an unknown type, more
+ * than MI_AOV_MAX_TYPES types, an unknown struct_size and a child in the scalar_spectral library (MI_ERR_INVALID, message in
+ * mi_last_error). mi_cancel() and timeout_s take effect between launches (MI_ERR_CANCELLED). */
+enum { MI_AOV_DEPTH = 0, MI_AOV_POSITION = 1, MI_AOV_UV = 2, MI_AOV_GEO_NORMAL = 3, MI_AOV_SH_NORMAL = 4,
+       MI_AOV_DP_DU = 5, MI_AOV_DP_DV = 6, MI_AOV_DUV_DX = 7, MI_AOV_DUV_DY = 8 };
+enum { MI_AOV_NESTED_NONE = 0, MI_AOV_NESTED_PATH = 1, MI_AOV_NESTED_DIRECT = 2 };
+#define MI_AOV_MAX_TYPES 32
+typedef struct {
+    uint32_t struct_size;            /* sizeof(mi_aov_cfg) of the caller: the library refuses a size it does not know */
+    uint32_t n_types;                /* <= MI_AOV_MAX_TYPES                                                         */
+    uint8_t  types[MI_AOV_MAX_TYPES];/* MI_AOV_*                                                                   */
+    int32_t  nested;                 /* MI_AOV_NESTED_*                                                            */
+    mi_sample_cfg child;             /* nested != NONE: the child integrator's parameters                          */
+} mi_aov_cfg;                        /* 19 words */
+/* 5 + N, or 0 for a description mi_render_aov would refuse for its types or sizes */
+int32_t   mi_aov_channel_count(const mi_aov_cfg *aov);
+mi_status mi_render_aov(mi_ctx *ctx, const mi_render_cfg *cfg, const mi_aov_cfg *aov, void *film);
+
 /* Integrator::cancel() — may be called from another thread */
 mi_status mi_cancel(mi_ctx *ctx);
 

@@ -145,7 +145,16 @@ class mi_sample_cfg(C.Structure):
                 ("emitter_samples", C.c_uint32), ("bsdf_samples", C.c_uint32), ("hide_emitters", C.c_int32), ("on_device", C.c_int32)]
 
 
+class mi_aov_cfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_types", C.c_uint32), ("types", C.c_uint8 * 32), ("nested", C.c_int32), ("child", mi_sample_cfg)]
+
+
 MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
+# mi_aov_cfg::types in the order of aov.cpp's grammar, and mi_aov_cfg::nested
+MI_AOV = dict(depth=0, position=1, uv=2, geo_normal=3, sh_normal=4, dp_du=5, dp_dv=6, duv_dx=7, duv_dy=8)
+MI_AOV_CHANNELS = dict(depth=1, position=3, uv=2, geo_normal=3, sh_normal=3, dp_du=3, dp_dv=3, duv_dx=2, duv_dy=2)
+MI_AOV_NESTED_NONE, MI_AOV_NESTED_PATH, MI_AOV_NESTED_DIRECT = 0, 1, 2
+MI_AOV_MAX_TYPES = 32
 # mi_bsdf::type (include/miwave.h); MASK / BLEND are wrappers whose children are other records (mi_bsdf::back, params[3])
 (MI_BSDF_DIFFUSE, MI_BSDF_DIELECTRIC, MI_BSDF_ROUGHCONDUCTOR, MI_BSDF_CONDUCTOR, MI_BSDF_PLASTIC, MI_BSDF_ROUGHDIELECTRIC,
  MI_BSDF_ROUGHPLASTIC, MI_BSDF_THINDIELECTRIC, MI_BSDF_NULL, MI_BSDF_MASK, MI_BSDF_BLEND) = range(11)
@@ -162,7 +171,8 @@ MI_SYMBOLS = ["mi_spectrum_channels", "mi_device_count", "mi_create", "mi_destro
               "mi_trace", "mi_render", "mi_cancel", "mi_get_counters", "mi_last_error", "mi_eval", "mi_selftest",
               "mi_ray_intersect", "mi_sample_emitter_direction", "mi_pdf_emitter_direction", "mi_emitter_eval", "mi_sample",
               "mi_film_alloc", "mi_film_free", "mi_film_download", "mi_film_reduce",
-              "mi_set_option", "mi_get_option", "mi_option_count", "mi_option_name", "mi_option_help"]
+              "mi_set_option", "mi_get_option", "mi_option_count", "mi_option_name", "mi_option_help",
+              "mi_render_aov", "mi_aov_channel_count"]
 
 
 VARIANT_SUFFIX = {"scalar_rgb": "", "scalar_spectral": "_spectral"}
@@ -221,6 +231,8 @@ def load_device_lib(variant="scalar_rgb"):
     lib.mi_emitter_eval.argtypes = [vp, sip, c_float_p, c_float_p, C.c_uint64]; lib.mi_emitter_eval.restype = C.c_int32
     # (the arrays are addresses: host or, with mi_sample_cfg::on_device, device memory)
     lib.mi_sample.argtypes = [vp, C.POINTER(mi_sample_cfg), C.POINTER(mi_rays_soa), vp, vp, vp, vp, vp, C.c_uint64]; lib.mi_sample.restype = C.c_int32
+    lib.mi_render_aov.argtypes = [vp, C.POINTER(mi_render_cfg), C.POINTER(mi_aov_cfg), vp]; lib.mi_render_aov.restype = C.c_int32
+    lib.mi_aov_channel_count.argtypes = [C.POINTER(mi_aov_cfg)]; lib.mi_aov_channel_count.restype = C.c_int32
     return lib
 
 
@@ -283,6 +295,10 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_sensor_create": (vp, [vp, vp, vp]), "mih_sensor_destroy": (None, [vp]),
         "mih_sensor_sample_ray": (i32, [vp, f, f, c_float_p]), "mih_sensor_x_fov": (f, [vp]),
         "mih_integrator_create": (vp, [vp]), "mih_integrator_destroy": (None, [vp]),
+        "mih_integrator_create_aov": (vp, [vp, C.POINTER(vp), C.POINTER(cp), u32]), "mih_integrator_aov_cfg": (i32, [vp, C.POINTER(mi_aov_cfg)]),
+        "mih_film_set_channels": (i32, [vp, cp, c_float_p, u64]), "mih_film_bitmap_channels": (i32, [vp, C.c_char_p, u32, c_float_p, u64]),
+        "mih_aov_fill": (i32, [i32, c_float_p, i32, c_float_p, c_float_p, i32, C.POINTER(C.c_uint8), u32, c_float_p, c_float_p]),
+        "mih_film_replay_pair": (i32, [C.POINTER(mi_render_cfg), c_float_p, c_float_p, c_float_p, c_float_p]),
         "mih_integrator_create_moment": (vp, [vp, vp, cp]), "mih_integrator_aov_names": (C.c_int, [vp, C.c_char_p, u32]),
         "mih_integrator_set_shard": (None, [vp, u32, u32]), "mih_integrator_set_profile": (None, [vp, i32]),
         "mih_integrator_set_plan": (None, [vp, i32]),

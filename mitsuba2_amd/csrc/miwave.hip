@@ -25,7 +25,7 @@
 #include <algorithm>
 
 #include "../../include/miwave.h"
-#if defined(MIW_NESTED_PART) || defined(MIW_LIGHTS_PART)   /* miwave_nested.hip, miwave_lights.hip: the kernel headers alone */
+#if defined(MIW_NESTED_PART) || defined(MIW_LIGHTS_PART) || defined(MIW_AOV_UNIT)   /* miwave_nested.hip, miwave_lights.hip, miwave_aov.hip: the kernel headers alone */
 #define MIW_KERNELS_ONLY 1
 #endif
 // Section clock (debug builds, -DMIW_SECTION_PROFILE=1): wall cycles per wavefront between markers, summed
@@ -110,6 +110,14 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/sample_kernel.h"
 #include "device/nested_instances.h"   /* a split build (-DMIW_SPLIT_NESTED=1) compiles the MATS_NESTED kernels in miwave_nested.hip */
 #include "device/lights_instances.h"   /* ... and (-DMIW_SPLIT_LIGHTS=1) the MATS_LIGHTS kernels in miwave_lights.hip */
+#if defined(MIW_AOV_UNIT) || !defined(MIW_KERNELS_ONLY)
+#include "miw/aov.h"
+#include "miw/film_gather_n.h"
+#include "device/aov_launch.h"         /* the aov integrator's kernels (mi_render_aov): compiled in miwave_aov.hip (-DMIW_SPLIT_AOV=1), else here */
+#if defined(MIW_AOV_UNIT) || !defined(MIW_SPLIT_AOV)
+#include "device/aov_kernel.h"
+#endif
+#endif
 
 #if !defined(MIW_KERNELS_ONLY)           /* (miwave_nested.hip includes this file for the kernels above alone) */
 __global__ void k_iota(uint32_t *out, uint32_t n) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = i; }
@@ -2590,6 +2598,8 @@ mi_status mi_selftest(mi_ctx *c, int32_t which, uint64_t *mismatches) {
     *mismatches = h;
     return MI_OK;
 }
+
+#include "aov_host.h"                  /* mi_render_aov, mi_aov_channel_count */
 
 } // extern "C"
 #endif // !MIW_KERNELS_ONLY

@@ -16,6 +16,8 @@
 #include "../csrc/miw/bsdf.h"
 #include "../csrc/miw/scene.h"
 #include "../csrc/miw/special.h"
+#include "../csrc/miw/aov.h"
+#include "../csrc/miw/film_gather_n.h"
 #include <cctype>
 
 namespace miwave {

@@ -198,6 +198,10 @@ public:
     const std::vector<float> &storage() const { return m_storage; }
     // develop: divide by W, XYZ -> linear sRGB (hdrfilm.cpp:251-322, bitmap.cpp:187-188)
     std::vector<float> bitmap_rgb() const;
+    // ... of a film with AOV channels (hdrfilm.cpp:265-319, MultiChannel): R G B blended from X Y Z, A, W dropped, every other
+    // channel under its own name; all of them divided by W. -> crop_w * crop_h * names.size() floats
+    std::vector<float> bitmap_channels(std::vector<std::string> &names) const;
+    const std::vector<std::string> &channels() const { return m_channels; }
     // HDRFilm::set_destination_file / develop (hdrfilm.cpp:213-217,327-345): writes bitmap() in `file_format`
     // ("openexr" (default) / "pfm"; "rgbe" is not provided), `pixel_format` rgb or rgba, `component_format`
     // float16 (default for OpenEXR) / float32; the extension is replaced by the format's proper one.
@@ -670,6 +674,29 @@ private:
     std::shared_ptr<SamplingIntegrator> m_nested; std::string m_name;
 };
 
+// src/integrators/aov.cpp: G-buffer channels beside at most ONE nested sampling integrator (`path` or `direct`, scalar_rgb build).
+// `aovs` is a list of <name>:<type> tokens separated by commas or spaces (string::tokenize's default delimiters), types depth,
+// position, uv, geo_normal, sh_normal, dp_du, dp_dv, duv_dx, duv_dy; aov_names() is the reference's: the string's channels, then
+// <child name>.R .G .B .A. render() fills a film of 5 + N channels through mi_render_aov (one context, no tile shards).
+class AOVIntegrator final : public SamplingIntegrator {
+public:
+    using Child = std::pair<std::string, std::shared_ptr<SamplingIntegrator>>;      // (name, integrator), props.objects()
+    explicit AOVIntegrator(const Properties &props, std::vector<Child> children = {});
+    bool render(Scene *scene, PerspectiveCamera *sensor) override;
+    void cancel() override;
+    std::vector<std::string> aov_names() const override { return m_aov_names; }
+    const std::vector<uint8_t> &aov_types() const { return m_aov_types; }             // MI_AOV_* per token
+    const std::shared_ptr<SamplingIntegrator> &nested() const { return m_nested; }
+    void fill_integrator(mi_render_cfg &cfg) const override;
+    void fill_aov_cfg(mi_aov_cfg &cfg) const;
+    // aov.cpp:156-254: sample() returns the AOVs beside the child's value, which mi_sample does not carry: refused
+    std::pair<Spectrum, bool> sample(const Scene *, IndependentSampler *, const Ray3f &, const float * = nullptr) const override;
+    void sample(const Scene *, const mi_rays_soa &, const float *, uint64_t *, const uint64_t *, float *, uint8_t *, uint64_t, bool = false) const override;
+private:
+    std::vector<uint8_t> m_aov_types; std::vector<std::string> m_aov_names;
+    std::shared_ptr<SamplingIntegrator> m_nested; std::string m_nested_name;
+};
+
 // PluginManager::create_object<Integrator>(props) for the integrators built here ("path", "direct")
 std::shared_ptr<SamplingIntegrator> make_integrator(const Properties &props);
 
@@ -677,7 +704,7 @@ std::shared_ptr<SamplingIntegrator> make_integrator(const Properties &props);
 // <scene>, <default>, <include>, <alias>, $parameters (also from `params`), <shape type="obj|ply|rectangle|sphere">, <bsdf> (inline, or
 // top-level with id + <ref id=.../>), <texture type="bitmap"> (PFM files; nested in a <bsdf> under the parameter's
 // name, or top-level with id + <ref id=... name=.../>), <emitter type="area">, <emitter type="envmap"> (PFM file), <sensor type="perspective"> with <film>,
-// <sampler>, <rfilter> children, <integrator type="path|direct">; values <float> <integer> <boolean> <string> <rgb>
+// <sampler>, <rfilter> children, <integrator type="path|direct">, <integrator type="moment|aov"> around a nested <integrator>; values <float> <integer> <boolean> <string> <rgb>
 // <spectrum value=...>; <transform name="to_world"> of <translate> <scale> <rotate> <lookat> <matrix>.
 // Anything else throws the reference's kind of error ("unexpected ..."/"Plugin ... not found").
 struct LoadedScene {

@@ -272,6 +272,77 @@ int mih_bsdf_sample_ctx(void *b, uint32_t mode, uint32_t type_mask, uint32_t com
         return 0; MIH_CATCH(-1)
 }
 
+// ---- the aov integrator's leaf arithmetic on the host build (csrc/miw/aov.h, csrc/miw/film_gather_n.h), for tests ----
+// shape: 0 mesh triangle (geom = p0 p1 p2 [+ 6 texture coordinates when has_tc]; hit = t, b1, b2), 1 rectangle, 2 sphere
+// (geom = to_world, to_object: 16 floats each, column-major; sphere: + centre xyz, radius, flip; hit = t). ray = o.xyz d.xyz. valid = 0: an invalid
+// interaction. out: aov_channels(types) floats; partials6 (may be NULL): dp_du, dp_dv.
+int mih_aov_fill(int shape, const float *geom, int has_tc, const float *ray6, const float *hit3, int valid, const uint8_t *types, uint32_t n_types, float *out, float *partials6) {
+    MIH_TRY
+        using namespace miw;
+        const V3 o = v3(ray6[0], ray6[1], ray6[2]), d = v3(ray6[3], ray6[4], ray6[5]);
+        SurfaceInteraction si; AovPartials pt;
+        if (shape == 0) {
+            const V3 p0 = ld3(geom), p1 = ld3(geom + 3), p2 = ld3(geom + 6);
+            const float *tc = has_tc ? geom + 9 : nullptr;
+            compute_surface_interaction(p0, p1, p2, nullptr, tc, hit3[0], hit3[1], hit3[2], d, si);
+            pt = aov_partials_triangle(p0, p1, p2, tc);
+        } else {
+            AnalyticRec r; std::memset(&r, 0, sizeof r);
+            std::memcpy(r.to_world, geom, 64); std::memcpy(r.to_object, geom + 16, 64);
+            if (shape == 1) {
+                r.kind = ANALYTIC_RECTANGLE;
+                const V3 du = xf_vector(r.to_world, v3(2.f, 0.f, 0.f)), dv = xf_vector(r.to_world, v3(0.f, 2.f, 0.f));
+                const V3 n = normalize(cross(du, dv));
+                st3(r.n, n); st3(r.dp_du, du); st3(r.dp_dv, dv);
+                float t, u, v;
+                ray_intersect_rectangle(r, o, d, 0.f, MIW_INFINITY, t, u, v);
+                compute_surface_interaction_rect(r, t, u, v, o, d, si);
+                pt = aov_partials_rect(r);
+            } else {
+                r.kind = ANALYTIC_SPHERE; r.n[0] = geom[32]; r.n[1] = geom[33]; r.n[2] = geom[34]; r.radius = geom[35]; r.flip = geom[36] != 0.f ? 1u : 0u;
+                compute_surface_interaction_sphere(r, hit3[0], o, d, si);
+                pt = aov_partials_sphere(r, si.p);
+            }
+        }
+        aov_fill(si, pt, valid != 0, types, n_types, out);
+        if (partials6) { st3(partials6, pt.dp_du); st3(partials6 + 3, pt.dp_dv); }
+        return (int) aov_channels(types, n_types); MIH_CATCH(-1)
+}
+// One log (pos: 2 floats, val: X Y Z A per sample, [pixel lane][sample], lanes = blocks * block_size^2 in row-major block order)
+// replayed by the five-channel film_block_replay + film_merge_texel (film5: w * h * 5) and by the N-channel functions with nch = 5 (filmN)
+int mih_film_replay_pair(const mi_render_cfg *cfg, const float *pos, const float *val, float *film5, float *filmN) {
+    MIH_TRY
+        using namespace miw;
+        FilmRec f; std::memset(&f, 0, sizeof f);
+        f.crop_w = cfg->crop_w; f.crop_h = cfg->crop_h; f.crop_x = cfg->crop_x; f.crop_y = cfg->crop_y; f.block_size = cfg->block_size; f.border = cfg->filter_border;
+        f.radius = cfg->filter_radius; f.scale_factor = (float) MIW_FILTER_RESOLUTION / cfg->filter_radius; std::memcpy(f.lut, cfg->filter_lut, sizeof f.lut);
+        const uint32_t bs = (uint32_t) cfg->block_size, bs2 = bs * bs, spp = cfg->spp;
+        uint32_t bs2_log2 = 0; while ((1u << bs2_log2) < bs2) ++bs2_log2;
+        const uint32_t bx = (cfg->crop_w + bs - 1) / bs, by = (cfg->crop_h + bs - 1) / bs, nt = bx * by, side = bs + 2u * (uint32_t) f.border;
+        if (cfg->block_count != nt) Throw("mih_film_replay_pair: block_ids must hold one entry per block");
+        const size_t lanes = (size_t) nt * bs2;
+        std::vector<int32_t> block_tile(nt); for (uint32_t t = 0; t < nt; ++t) block_tile[t] = (int32_t) t;
+        std::vector<U4> st(lanes); for (U4 &s : st) { s.x = s.y = s.z = 0; s.w = spp; }
+        std::vector<F2> lp(lanes * spp); std::vector<F4> lv(lanes * spp); std::vector<float> logn(lanes * spp * 6);
+        for (size_t i = 0; i < lanes * spp; ++i) {
+            lp[i].x = pos[2 * i]; lp[i].y = pos[2 * i + 1]; lv[i].x = val[4 * i]; lv[i].y = val[4 * i + 1]; lv[i].z = val[4 * i + 2]; lv[i].w = val[4 * i + 3];
+            logn[6 * i] = pos[2 * i]; logn[6 * i + 1] = pos[2 * i + 1]; for (int k = 0; k < 4; ++k) logn[6 * i + 2 + k] = val[4 * i + k];
+        }
+        BlockReplayArgs a{}; a.log_pos = lp.data(); a.log_val = lv.data(); a.log_rec = nullptr; a.st = st.data(); a.spp = spp; a.block_ids = cfg->block_ids;
+        a.block_tile = block_tile.data(); a.tile_list = nullptr; a.blocks_x = bx; a.blocks_y = by; a.bs2_log2 = bs2_log2; a.tile_stride = side * side * 5u;
+        BlockReplayArgsN n{}; n.log = logn.data(); n.stride = 6; n.nch = 5; n.spp = spp; n.block_ids = cfg->block_ids; n.block_tile = block_tile.data(); n.tile_list = nullptr;
+        n.blocks_x = bx; n.blocks_y = by; n.bs2_log2 = bs2_log2; n.tile_stride = side * side * 5u; n.tile0 = 0;
+        std::vector<float> t5((size_t) nt * a.tile_stride, 0.f), tn((size_t) nt * n.tile_stride, 0.f);
+        for (uint32_t t = 0; t < nt; ++t) { film_block_replay(f, a, t, t5.data() + (size_t) t * a.tile_stride); film_block_replay_n(f, n, t, tn.data() + (size_t) t * n.tile_stride); }
+        for (int y = 0; y < f.crop_h; ++y)
+            for (int x = 0; x < f.crop_w; ++x) {
+                const size_t i = ((size_t) y * f.crop_w + x) * 5;
+                film_merge_texel(f, a, t5.data(), x, y, film5 + i);
+                for (uint32_t k = 0; k < 5; ++k) filmN[i + k] = film_merge_channel_n(f, n, tn.data(), x, y, k);
+            }
+        return 0; MIH_CATCH(-1)
+}
+
 void *mih_film_create(void *props) { MIH_TRY return new Box<Film>{ std::make_shared<Film>(*(Properties *) props) }; MIH_CATCH(nullptr) }
 void mih_film_destroy(void *f) { delete (Box<Film> *) f; }
 int mih_film_set_filter(void *f, const char *name, void *props) {
@@ -301,6 +372,25 @@ int mih_film_set_data(void *f, const float *xyzaw, uint64_t count) {
         if (count != film.storage().size()) Throw("film data size mismatch");
         std::memcpy(film.storage().data(), xyzaw, count * sizeof(float));
         return 0; MIH_CATCH(-1)
+}
+// a film with named channels (`names`: comma-separated, X,Y,Z,A,W first), filled with `data`; throws what Film::prepare throws
+int mih_film_set_channels(void *f, const char *names, const float *data, uint64_t count) {
+    MIH_TRY
+        Film &film = *((Box<Film> *) f)->p;
+        std::vector<std::string> ch; std::string cur;
+        for (const char *c = names; ; ++c) { if (*c == ',' || !*c) { ch.push_back(cur); cur.clear(); if (!*c) break; } else cur += *c; }
+        film.prepare(ch);
+        if (data) { if (count != film.storage().size()) Throw("film data size mismatch"); std::memcpy(film.storage().data(), data, count * sizeof(float)); }
+        return 0; MIH_CATCH(-1)
+}
+// Film::bitmap() of a film with AOV channels: comma-separated channel names into `names`, the pixels into `out` (cap floats) -> channel count
+int mih_film_bitmap_channels(void *f, char *names, uint32_t names_cap, float *out, uint64_t cap) {
+    MIH_TRY
+        std::vector<std::string> nm; const std::vector<float> px = ((Box<Film> *) f)->p->bitmap_channels(nm);
+        std::string s; for (const std::string &n : nm) s += (s.empty() ? "" : ",") + n;
+        if (s.size() + 1 > names_cap || px.size() > cap) Throw("mih_film_bitmap_channels: buffer too small");
+        std::memcpy(names, s.c_str(), s.size() + 1); std::memcpy(out, px.data(), px.size() * sizeof(float));
+        return (int) nm.size(); MIH_CATCH(-1)
 }
 void mih_film_crop_size(void *f, int *w, int *h) { auto cs = ((Box<Film> *) f)->p->crop_size(); *w = cs[0]; *h = cs[1]; }
 static thread_local std::string g_develop_path;
@@ -344,6 +434,19 @@ void *mih_integrator_create(void *props) {
 }
 void *mih_integrator_create_moment(void *props, void *nested, const char *name) {
     MIH_TRY return new Box<SamplingIntegrator>{ std::make_shared<MomentIntegrator>(*(Properties *) props, ((Box<SamplingIntegrator> *) nested)->p, name ? name : "integrator") }; MIH_CATCH(nullptr)
+}
+// AOVIntegrator(props, children): `nested` / `names`: n child integrators and their names (n = 0: none)
+void *mih_integrator_create_aov(void *props, void *const *nested, const char *const *names, uint32_t n) {
+    MIH_TRY
+        std::vector<AOVIntegrator::Child> children;
+        for (uint32_t k = 0; k < n; ++k) children.push_back({ names && names[k] ? names[k] : "integrator", ((Box<SamplingIntegrator> *) nested[k])->p });
+        return new Box<SamplingIntegrator>{ std::make_shared<AOVIntegrator>(*(Properties *) props, std::move(children)) }; MIH_CATCH(nullptr)
+}
+// the mi_aov_cfg an aov integrator renders with; -1: not an aov integrator
+int mih_integrator_aov_cfg(void *i, mi_aov_cfg *cfg) {
+    MIH_TRY auto *a = dynamic_cast<AOVIntegrator *>(((Box<SamplingIntegrator> *) i)->p.get());
+        if (!a) throw std::runtime_error("not an aov integrator");
+        a->fill_aov_cfg(*cfg); return 0; MIH_CATCH(-1)
 }
 int mih_integrator_aov_names(void *i, char *buf, uint32_t cap) {       // comma-separated
     MIH_TRY std::string s; for (const std::string &n : ((Box<SamplingIntegrator> *) i)->p->aov_names()) s += (s.empty() ? "" : ",") + n;

@@ -25,6 +25,13 @@ Film::Film(const Properties &props) {
     if (m_file_format == "pfm") { m_pixel_format = "rgb"; m_component_format = "float32"; }      // :170-180
 }
 void Film::prepare(const std::vector<std::string> &channels) {
+    // hdrfilm.cpp:190-199: no two channels of one name, R G B (what X Y Z develop to) included. (The reference's loop runs to
+    // channels.size(), three short of the sorted list's end, and so misses duplicates that sort last; every entry is compared here.)
+    std::vector<std::string> sorted = channels;
+    sorted.push_back("R"); sorted.push_back("G"); sorted.push_back("B");
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 1; i < sorted.size(); ++i)
+        if (sorted[i] == sorted[i - 1]) Throw("Film::prepare(): duplicate channel name \"" + sorted[i] + "\"");
     m_channels = channels;
     m_storage.assign((size_t) m_crop_size[0] * m_crop_size[1] * channels.size(), 0.f);
 }
@@ -39,6 +46,24 @@ std::vector<float> Film::bitmap_rgb() const {
         rgb[i * 3] = c.x; rgb[i * 3 + 1] = c.y; rgb[i * 3 + 2] = c.z;
     }
     return rgb;
+}
+
+// hdrfilm.cpp:265-319: the MultiChannel bitmap of a film with AOV channels
+std::vector<float> Film::bitmap_channels(std::vector<std::string> &names) const {
+    const size_t n = (size_t) m_crop_size[0] * m_crop_size[1], stride = std::max<size_t>(m_channels.size(), 5);
+    names = { "R", "G", "B", "A" };
+    for (size_t k = 5; k < m_channels.size(); ++k) names.push_back(m_channels[k]);
+    const size_t out_n = names.size();
+    std::vector<float> out(n * out_n);
+    for (size_t i = 0; i < n; ++i) {
+        const float *p = &m_storage[i * stride];
+        const float inv_w = p[4] != 0.f ? 1.f / p[4] : 0.f;   // struct.cpp:1734-1745 weight normalisation
+        const miw::V3 c = miw::xyz_to_srgb(miw::v3(p[0] * inv_w, p[1] * inv_w, p[2] * inv_w));
+        float *o = &out[i * out_n];
+        o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = p[3] * inv_w;
+        for (size_t k = 5; k < stride; ++k) o[k - 1] = p[k] * inv_w;
+    }
+    return out;
 }
 
 // float32 -> IEEE half, round to nearest even (what Bitmap::convert does for component_format float16)
@@ -69,6 +94,8 @@ std::string Film::develop() const {
     if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) path = path.substr(0, dot);
     path += ext;
     const int W = m_crop_size[0], H = m_crop_size[1];
+    const bool has_aovs = m_channels.size() > 5;               // hdrfilm.cpp:265
+    if (has_aovs && !exr) Throw("A film with AOV channels cannot be written as PFM (three channels); use file_format \"openexr\"");
     std::vector<float> rgb = bitmap_rgb();
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) Throw("Could not open \"" + path + "\" for writing");
@@ -80,7 +107,13 @@ std::string Film::develop() const {
     }
     // OpenEXR 2, single-part scanline image, no compression
     const bool half = m_component_format != "float32";
-    const int nch = rgba ? 4 : 3; const char *names = rgba ? "ABGR" : "BGR";      // channels are stored alphabetically
+    // channels are stored alphabetically; a film with AOV channels writes the MultiChannel bitmap: R G B A and every named channel
+    std::vector<std::string> mc_names; std::vector<float> mc;
+    if (has_aovs) mc = bitmap_channels(mc_names);
+    std::vector<size_t> order(mc_names.size());
+    for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return mc_names[a] < mc_names[b]; });
+    const int nch = has_aovs ? (int) mc_names.size() : rgba ? 4 : 3; const char *names = rgba ? "ABGR" : "BGR";
     std::vector<unsigned char> hdr;
     auto put = [&](const void *p, size_t n) { hdr.insert(hdr.end(), (const unsigned char *) p, (const unsigned char *) p + n); };
     auto put_str = [&](const char *s) { put(s, std::strlen(s) + 1); };
@@ -89,8 +122,10 @@ std::string Film::develop() const {
     auto attr = [&](const char *name, const char *type, int32_t size) { put_str(name); put_str(type); put_i32(size); };
     const uint32_t magic = 20000630u, version = 2u;
     put(&magic, 4); put(&version, 4);
-    attr("channels", "chlist", nch * 18 + 1);
-    for (int c = 0; c < nch; ++c) { char nm[2] = { names[c], 0 }; put_str(nm); put_i32(half ? 1 : 2); unsigned char z[4] = { 0, 0, 0, 0 }; put(z, 4); put_i32(1); put_i32(1); }
+    size_t name_bytes = 0;
+    for (int c = 0; c < nch; ++c) name_bytes += has_aovs ? mc_names[order[c]].size() : 1;
+    attr("channels", "chlist", (int32_t) (nch * 17 + name_bytes + 1));
+    for (int c = 0; c < nch; ++c) { char nm[2] = { has_aovs ? ' ' : names[c], 0 }; put_str(has_aovs ? mc_names[order[c]].c_str() : nm); put_i32(half ? 1 : 2); unsigned char z[4] = { 0, 0, 0, 0 }; put(z, 4); put_i32(1); put_i32(1); }
     { unsigned char z = 0; put(&z, 1); }
     attr("compression", "compression", 1); { unsigned char z = 0; put(&z, 1); }
     attr("dataWindow", "box2i", 16); put_i32(0); put_i32(0); put_i32(W - 1); put_i32(H - 1);
@@ -109,11 +144,12 @@ std::string Film::develop() const {
         int32_t yy = y, sz = (int32_t) line_bytes;
         std::fwrite(&yy, 4, 1, f); std::fwrite(&sz, 4, 1, f);
         for (int c = 0; c < nch; ++c) {
-            const char ch = names[c];
+            const char ch = has_aovs ? ' ' : names[c];
             for (int x = 0; x < W; ++x) {
                 const size_t i = (size_t) y * W + x;
                 float v;
-                if (ch == 'A') { const float *p = &m_storage[i * std::max<size_t>(m_channels.size(), 5)]; v = p[4] != 0.f ? p[3] / p[4] : 0.f; }
+                if (has_aovs) v = mc[i * mc_names.size() + order[c]];
+                else if (ch == 'A') { const float *p = &m_storage[i * std::max<size_t>(m_channels.size(), 5)]; v = p[4] != 0.f ? p[3] / p[4] : 0.f; }
                 else v = rgb[i * 3 + (ch == 'R' ? 0 : ch == 'G' ? 1 : 2)];
                 unsigned char *dst = &line[((size_t) c * W + x) * bpc];
                 if (half) { uint16_t h = float_to_half(v); std::memcpy(dst, &h, 2); } else std::memcpy(dst, &v, 4);

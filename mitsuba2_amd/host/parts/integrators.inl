@@ -1,4 +1,4 @@
-// libmiwave_host: SamplingIntegrator machinery, path / direct / moment integrators.
+// libmiwave_host: SamplingIntegrator machinery, path / direct / moment / aov integrators.
 // Part of the single translation unit host/miwave_host.cpp (included there, in this order).
 // ============================================================================================
 // PathIntegrator
@@ -38,6 +38,7 @@ void DirectIntegrator::fill_integrator(mi_render_cfg &cfg) const {
 }
 std::shared_ptr<SamplingIntegrator> make_integrator(const Properties &props) {
     if (props.plugin_name() == "moment") Throw("moment: needs a nested integrator (MomentIntegrator(props, nested))");
+    if (props.plugin_name() == "aov") return std::make_shared<AOVIntegrator>(props);
     if (props.plugin_name() == "path") return std::make_shared<PathIntegrator>(props);
     if (props.plugin_name() == "direct") return std::make_shared<DirectIntegrator>(props);
     Throw("Plugin \"" + props.plugin_name() + "\" not found!");
@@ -295,4 +296,93 @@ std::pair<Spectrum, bool> MomentIntegrator::sample(const Scene *, IndependentSam
 }
 void MomentIntegrator::sample(const Scene *, const mi_rays_soa &, const float *, uint64_t *, const uint64_t *, float *, uint8_t *, uint64_t, bool) const {
     Throw("moment: sample() returns AOVs, which the device entry point does not serve (NotImplementedError)");
+}
+
+// ============================================================================================
+// AOVIntegrator (src/integrators/aov.cpp)
+// ============================================================================================
+// string::tokenize (src/libcore/string.cpp:7-25), include_empty = false
+static std::vector<std::string> tokenize(const std::string &str, const std::string &delim = ", ") {
+    std::vector<std::string> tokens;
+    std::string::size_type last_pos = 0, pos = str.find_first_of(delim, last_pos);
+    while (last_pos != std::string::npos) {
+        std::string sub = str.substr(last_pos, pos - last_pos);
+        if (!sub.empty()) tokens.push_back(std::move(sub));
+        last_pos = pos;
+        if (last_pos != std::string::npos) { last_pos += 1; pos = str.find_first_of(delim, last_pos); }
+    }
+    return tokens;
+}
+// aov.cpp:83-154
+AOVIntegrator::AOVIntegrator(const Properties &props, std::vector<Child> children) : SamplingIntegrator(props) {
+    static const struct { const char *name; uint8_t type; const char *suffix[3]; } table[] = {
+        { "depth", MI_AOV_DEPTH, { "", nullptr, nullptr } }, { "position", MI_AOV_POSITION, { ".X", ".Y", ".Z" } },
+        { "uv", MI_AOV_UV, { ".U", ".V", nullptr } }, { "geo_normal", MI_AOV_GEO_NORMAL, { ".X", ".Y", ".Z" } },
+        { "sh_normal", MI_AOV_SH_NORMAL, { ".X", ".Y", ".Z" } }, { "dp_du", MI_AOV_DP_DU, { ".X", ".Y", ".Z" } },
+        { "dp_dv", MI_AOV_DP_DV, { ".X", ".Y", ".Z" } }, { "duv_dx", MI_AOV_DUV_DX, { ".U", ".V", nullptr } },
+        { "duv_dy", MI_AOV_DUV_DY, { ".U", ".V", nullptr } } };
+    for (const std::string &token : tokenize(props.string("aovs", ""))) {
+        const std::vector<std::string> item = tokenize(token, ":");
+        if (item.size() != 2 || item[0].empty() || item[1].empty()) Throw("Invalid AOV specification: require <name>:<type> pair");
+        bool found = false;
+        for (const auto &t : table)
+            if (item[1] == t.name) {
+                m_aov_types.push_back(t.type);
+                for (const char *sfx : t.suffix) if (sfx) m_aov_names.push_back(item[0] + sfx);
+                found = true;
+            }
+        if (!found) Throw("Invalid AOV type \"" + item[1] + "\"!");
+    }
+    if (m_aov_types.size() > MI_AOV_MAX_TYPES) Throw("aov: more than " + std::to_string(MI_AOV_MAX_TYPES) + " AOV types");
+    if (children.size() > 1) Throw("aov: more than one nested integrator is not provided by this layer");
+    for (Child &kv : children) {                                // :137-150
+        if (!kv.second) Throw("Child objects must be of type 'SamplingIntegrator'!");
+        if (dynamic_cast<MomentIntegrator *>(kv.second.get()) || dynamic_cast<AOVIntegrator *>(kv.second.get()))
+            Throw("aov: a nested moment or aov integrator is not provided by this layer (path and direct are)");
+        m_nested = kv.second; m_nested_name = kv.first;
+        for (const char *sfx : { ".R", ".G", ".B", ".A" }) m_aov_names.push_back(kv.first + sfx);
+    }
+}
+void AOVIntegrator::cancel() { SamplingIntegrator::cancel(); if (m_nested) m_nested->cancel(); }
+void AOVIntegrator::fill_integrator(mi_render_cfg &cfg) const {
+    if (m_nested) m_nested->fill_integrator(cfg);
+    else { cfg.integrator = MI_INTEGRATOR_PATH; cfg.max_depth = -1; cfg.rr_depth = 5; }   // (not read by mi_render_aov)
+}
+void AOVIntegrator::fill_aov_cfg(mi_aov_cfg &a) const {
+    std::memset(&a, 0, sizeof a);
+    a.struct_size = (uint32_t) sizeof a; a.n_types = (uint32_t) m_aov_types.size();
+    for (size_t i = 0; i < m_aov_types.size(); ++i) a.types[i] = m_aov_types[i];
+    a.nested = MI_AOV_NESTED_NONE;
+    if (m_nested) {
+        m_nested->fill_sample_cfg(a.child);
+        a.nested = a.child.integrator == MI_INTEGRATOR_DIRECT ? MI_AOV_NESTED_DIRECT : MI_AOV_NESTED_PATH;
+    }
+}
+bool AOVIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
+    if (!scene || !sensor) Throw("render(): null scene or sensor");
+    if (!scene->ctx()) Throw("render(): the scene has no device context (Scene::build(device >= 0) first)");
+    if (scene->device_count() > 1 || m_world > 1) Throw("aov: a frame with AOV channels is rendered by one context (no multi-GPU scenes, no tile shards)");
+    Film *film = sensor->film().get();
+    std::vector<std::string> channels = { "X", "Y", "Z", "A", "W" };        // integrator.cpp:67-73
+    for (const std::string &n : m_aov_names) channels.push_back(n);
+    film->prepare(channels);
+    mi_aov_cfg acfg; fill_aov_cfg(acfg);
+    const uint32_t passes = pass_count(sensor);
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        mi_render_cfg cfg; std::vector<uint32_t> block_ids, tiles;
+        make_render_cfg(sensor, cfg, block_ids, tiles, 1, pass);
+        cfg.samples_per_launch = 0;
+        m_active_ctx.store(scene->ctx());
+        const mi_status st = mi_render_aov(scene->ctx(), &cfg, &acfg, film->storage().data());
+        m_active_ctx.store(nullptr);
+        if (st == MI_ERR_CANCELLED) return false;
+        if (st != MI_OK) Throw(std::string("mi_render_aov: ") + mi_last_error(scene->ctx()));
+    }
+    return true;
+}
+std::pair<Spectrum, bool> AOVIntegrator::sample(const Scene *, IndependentSampler *, const Ray3f &, const float *) const {
+    Throw("aov: sample() returns AOVs, which the device entry point does not serve (NotImplementedError)");
+}
+void AOVIntegrator::sample(const Scene *, const mi_rays_soa &, const float *, uint64_t *, const uint64_t *, float *, uint8_t *, uint64_t, bool) const {
+    Throw("aov: sample() returns AOVs, which the device entry point does not serve (NotImplementedError)");
 }

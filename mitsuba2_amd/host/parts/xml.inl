@@ -263,13 +263,23 @@ LoadedScene load_xml_string(const std::string &xml, const std::map<std::string, 
         else if (n.tag == "texture") { if (!n.attr.count("id")) Throw("Error while loading XML: a top-level <texture> needs an id"); parse_texture(cx, n); }
         else if (n.tag == "integrator") {
             Properties p(cx.get(n, "type"));
-            if (p.plugin_name() != "path" && p.plugin_name() != "direct" && p.plugin_name() != "moment") Throw("Plugin \"" + p.plugin_name() + "\" not found!");
+            if (p.plugin_name() != "path" && p.plugin_name() != "direct" && p.plugin_name() != "moment" && p.plugin_name() != "aov") Throw("Plugin \"" + p.plugin_name() + "\" not found!");
             auto objs = parse_properties(cx, n, p);
             if (p.plugin_name() == "moment") {                 // <integrator type="moment"><integrator type="path" name=.../></integrator>
                 if (objs.size() != 1 || objs[0]->tag != "integrator") Throw("Error while loading XML: <integrator type=\"moment\"> takes one nested <integrator> in this layer");
                 Properties np(cx.get(*objs[0], "type"));
                 if (!parse_properties(cx, *objs[0], np).empty()) Throw("Error while loading XML: unexpected object inside the nested <integrator>");
                 out.integrator = std::make_shared<MomentIntegrator>(p, make_integrator(np), cx.get(*objs[0], "name", "integrator"));
+            } else if (p.plugin_name() == "aov") {             // <integrator type="aov"><string name="aovs" .../><integrator type="path" name=.../></integrator>
+                std::vector<AOVIntegrator::Child> children;
+                for (const XmlNode *o : objs) {
+                    if (o->tag != "integrator") Throw("Error while loading XML: unexpected <" + o->tag + "> inside <integrator>");
+                    Properties np(cx.get(*o, "type"));
+                    if (np.plugin_name() != "path" && np.plugin_name() != "direct") Throw("Error while loading XML: <integrator type=\"aov\"> nests \"path\" or \"direct\" in this layer, not \"" + np.plugin_name() + "\"");
+                    if (!parse_properties(cx, *o, np).empty()) Throw("Error while loading XML: unexpected object inside the nested <integrator>");
+                    children.push_back({ cx.get(*o, "name", "integrator"), make_integrator(np) });
+                }
+                out.integrator = std::make_shared<AOVIntegrator>(p, std::move(children));
             } else {
                 if (!objs.empty()) Throw("Error while loading XML: unexpected <" + objs[0]->tag + "> inside <integrator>");
                 out.integrator = make_integrator(p);
