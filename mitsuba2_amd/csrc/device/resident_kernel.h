@@ -303,7 +303,9 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
     }
     LaneCounters local; local.segments = local.samples = local.shadow_rays = 0;
     auto tr2 = [&](V3 o, float mint, V3 dE, float maxtE, bool hasE, V3 dS, float maxtS, bool hasS, F4 &hE, bool &occS) {
-        trace2<Tiny, Analytic>(sc, cfg, smem, o, mint, dE, maxtE, hasE, dS, maxtS, hasS, hE, occS);
+        // (LeafPairs: the leaf pass on pre-widened operands, trace.h — not in the direct-integrator kernels: compiled for three wavefronts per SIMD they keep ~40 values in
+        // scratch as it is, and with it the MATS_LIGHTS one keeps 184 B per lane where tests/test_lights_kernel_budget.py allows 152)
+        trace2<Tiny, Analytic, Integ != INTEG_DIRECT>(sc, cfg, smem, o, mint, dE, maxtE, hasE, dS, maxtS, hasS, hE, occS);
     };
     if (UseLog) {
         QueueWork<Tiny != 0, false, Groups> work; work.Q = &Q; work.next_pixel = next_pixel; work.n_lanes = P.n_lanes; work.spp = P.spp; work.lane = 0; work.warn_negative = P.film.warn_negative;

@@ -240,6 +240,39 @@ __device__ __forceinline__ bool leaf_box_test_octant(const LeafBox &b, const Fas
     tf = __builtin_fmaf(abs_(tf), 2e-6f, tf);
     return tn <= tf && tn <= tmax_wide;
 }
+// The octant test with the widening of the exit distance taken out of the leaf loop (the render kernels' trace2): the exit half of every
+// packed operand carries the widening, {inv_d, inv_d'} and {c, c'} with inv_d' = inv_d * (1 + w') and c' = -o * inv_d' pushed up by
+// |c'| * 2^-21, so the packed fma of an axis yields (entry distance, WIDENED exit distance) and the loop holds neither the |tf| nor the fma
+// of the form above. The entry half is the same fma on the same operands: tn has the bits it had. The exit distance only has to be no
+// smaller than the other form's for every box that form accepts (tools/leaf_pass_check.cpp asserts exactly that):
+//   * exactly, p * inv_d' + c' = (p - o) * inv_d * (1 + w') up to one rounding of inv_d' (relative, common to both terms) and one of c'
+//     (absolute, |c| * 2^-24) — the error the other form's c = fl(-o * inv_d) has as well, in either direction. w' = 2.5e-6 is the other
+//     form's w = 2e-6 plus 8 x 2^-24 for the relative roundings of the two forms; the push of |c'| * 2^-21 = 8 x 2^-24 x |c'| covers the
+//     absolute ones, which dominate when the origin is far from the scene's origin and close to the plane (p * inv_d and c cancel);
+//   * a box BEHIND the ray (tf < 0) has its exit moved away from zero instead of towards it; it fails tn >= mint >= 0 > tf in both forms
+//     (mint >= 0: the render kernels' rays; mi_sample's caller-supplied mint keeps the form above).
+// Both terms are far below the boxes' padding of 1e-5 x the scene extent (bvh_build.h), like the widening itself.
+struct LeafRay { miw_f2 ix, iy, iz, cx, cy, cz; float mint; };
+#define MIW_LEAF_WIDEN 1.0000025f          /* 1 + w' */
+#define MIW_LEAF_PUSH  4.76837158e-7f      /* 2^-21 */
+__device__ __forceinline__ LeafRay leaf_ray(const FastRay &r, V3 o) {
+    LeafRay l;
+    l.ix = (miw_f2) { r.inv_d.x, r.inv_d.x * MIW_LEAF_WIDEN }; l.iy = (miw_f2) { r.inv_d.y, r.inv_d.y * MIW_LEAF_WIDEN }; l.iz = (miw_f2) { r.inv_d.z, r.inv_d.z * MIW_LEAF_WIDEN };
+    l.cx = -((miw_f2) { o.x, o.x } * l.ix); l.cy = -((miw_f2) { o.y, o.y } * l.iy); l.cz = -((miw_f2) { o.z, o.z } * l.iz);      // .x: the bits of r.neg_o_inv_d
+    l.cx.y = __builtin_fmaf(abs_(l.cx.y), MIW_LEAF_PUSH, l.cx.y); l.cy.y = __builtin_fmaf(abs_(l.cy.y), MIW_LEAF_PUSH, l.cy.y); l.cz.y = __builtin_fmaf(abs_(l.cz.y), MIW_LEAF_PUSH, l.cz.y);
+    l.mint = r.mint;
+    return l;
+}
+__device__ __forceinline__ bool leaf_box_test_octant(const LeafBox &b, const LeafRay &r, float tmax_wide) {
+    const miw_f2 px = { b.p[0], b.p[1] }, py = { b.p[2], b.p[3] }, pz = { b.p[4], b.p[5] };
+    const miw_f2 tx = __builtin_elementwise_fma(px, r.ix, r.cx), ty = __builtin_elementwise_fma(py, r.iy, r.cy), tz = __builtin_elementwise_fma(pz, r.iz, r.cz);
+    // max(tn, mint) <= tf as two compares: mint as the operand of a maximum is canonicalised by the compiler inside the loop, every time
+    // (v_max_f32 m, m, m; values cross basic blocks as unknowns); as the operand of a compare it is not. mint <= tmax_wide is not asked:
+    // it does not depend on the box, and a ray with mint > maxt has no hit the exact test accepts.
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(tx.x, ty.x), tz.x);
+    const float tf = __builtin_fminf(__builtin_fminf(tx.y, ty.y), tz.y);
+    return tn <= tf && r.mint <= tf && tn <= tmax_wide;
+}
 __device__ __forceinline__ uint32_t ray_octant(const FastRay &r) {
     return (r.inv_d.x < 0.f ? 1u : 0u) | (r.inv_d.y < 0.f ? 2u : 0u) | (r.inv_d.z < 0.f ? 4u : 0u);
 }
@@ -462,7 +495,8 @@ __device__ __forceinline__ bool trace_one(const SceneView &sc, TraceLds cfg, con
 // "any triangle passes" for S.
 // `Tiny` selects the code that is compiled in: the two-phase LDS query (tiny scenes) or the tree walks —
 // one kernel per scene class keeps each one's register budget (occupancy) to what it needs.
-template <int Tiny, bool Analytic = true>
+// `LeafPairs`: the leaf pass runs on LeafRay operands (the widening hoisted out of its loop; rays with mint >= 0 — the render kernels).
+template <int Tiny, bool Analytic = true, bool LeafPairs = false>
 __device__ __forceinline__ void trace2(const SceneView &sc, TraceLds cfg, const uint4 *smem,
                                        V3 o, float mint, V3 dE, float maxtE, bool hasE,
                                        V3 dS, float maxtS, bool hasS, F4 &hit_out, bool &occ_out) {
@@ -482,11 +516,14 @@ __device__ __forceinline__ void trace2(const SceneView &sc, TraceLds cfg, const 
         Mask mE = 0, mS = 0;
 #if MIW_OCTANT_BOXES
         const LeafBox *lbE = lb + ray_octant(rE), *lbS = lb + ray_octant(rS);   // each ray reads the copies of its own octant
+        using LeafOperands = typename std::conditional<LeafPairs, LeafRay, FastRay>::type;
+        LeafOperands qE, qS;
+        if constexpr (LeafPairs) { qE = leaf_ray(rE, o); qS = leaf_ray(rS, o); } else { qE = rE; qS = rS; }
         for (uint32_t i = 0; i < cfg.leaves; ++i) {
             const LeafBox &bE = lbE[8u * i], &bS = lbS[8u * i];
             const Mask bits = Tiny == 2 ? (Mask) bE.mask_lo : (Mask) (bE.mask_lo | ((unsigned long long) bE.mask_hi << 32));
-            if (leaf_box_test_octant(bE, rE, wideE)) mE |= bits;
-            if (leaf_box_test_octant(bS, rS, wideS)) mS |= bits;
+            if (leaf_box_test_octant(bE, qE, wideE)) mE |= bits;
+            if (leaf_box_test_octant(bS, qS, wideS)) mS |= bits;
         }
 #else
         for (uint32_t i = 0; i < cfg.leaves; ++i) {

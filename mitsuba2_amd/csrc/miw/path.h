@@ -220,7 +220,14 @@ struct LogSink16 {
     MIW_HD void operator()(uint32_t pixel, uint32_t sample_idx, V2 pos, const float *aovs) const {
         const size_t i = log_index(il, lane, spp, sample_idx);
         U4 r; r.x = r.y = r.z = 0u; r.w = film_pack_meta(rej, rej, false);
-        if (sample_is_valid(aovs, film->warn_negative != 0)) {
+        // sample_is_valid (film.h) without its short-circuit evaluation, the same predicate as straight-line compares: every value finite, and
+        // (warn_negative) the least of them >= -1e-5 — the minimum of finite values is one of them, and with a value that is not finite the
+        // sample is rejected whatever the minimum
+        float least = aovs[0];
+        bool ok = isfinite_(aovs[0]);
+        for (int k = 1; k < MIW_FILM_CHANNELS; ++k) { least = __builtin_fminf(least, aovs[k]); ok = ok & isfinite_(aovs[k]); }
+        ok = ok & ((film->warn_negative == 0) | (least >= -1e-5f));
+        if (ok) {
             const uint32_t cx = film_class_of(thr, film_phase(*film, pos.x, (int) (pixel & 0xffffu), film->crop_x)),
                            cy = film_class_of(thr, film_phase(*film, pos.y, (int) (pixel >> 16), film->crop_y));
             r.x = f2u(aovs[0]); r.y = f2u(aovs[1]); r.z = f2u(aovs[2]); r.w = film_pack_meta(cx, cy, aovs[3] != 0.f);
