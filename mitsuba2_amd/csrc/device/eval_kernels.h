@@ -4,7 +4,7 @@ struct SoaRays { const float *ox, *oy, *oz, *dx, *dy, *dz, *mint, *maxt; };
 struct SoaHits { float *t, *u, *v; uint32_t *prim, *shape; };
 
 #ifndef MIW_KERNEL
-#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_class.hip, which includes this header into further objects of the library, keeps it out of them */
 #endif
 template <bool AnyHit>
 __global__ __launch_bounds__(MIW_BLOCK) void k_trace_soa(SceneView sc, SoaRays R, SoaHits H, uint64_t n, TraceLds cfg) {

@@ -1,5 +1,5 @@
 #ifndef MIW_KERNEL
-#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_class.hip, which includes this header into further objects of the library, keeps it out of them */
 #endif
 // Plan 2 (resident): k_init_pixels, the shared pixel queue and k_path_resident (path / direct integrators).
 // Part of the single translation unit csrc/miwave.hip (included there, in this order; not a stand-alone header).

@@ -65,7 +65,7 @@ __device__ __forceinline__ bool init_one_lane(const RenderParams &P, const LaneQ
 }
 
 #ifndef MIW_KERNEL
-#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_nested.hip, which includes this header into further objects of the library, keeps it out of them */
+#define MIW_KERNEL __global__           /* a kernel that is no template: miwave_class.hip, which includes this header into further objects of the library, keeps it out of them */
 #endif
 MIW_KERNEL __launch_bounds__(MIW_BLOCK) void k_init_lanes(RenderParams P, LaneQueues Q, uint32_t *pixel_out, InitArgs A, WorkLists W) {
     __shared__ uint32_t s_cnt[WL_LISTS];

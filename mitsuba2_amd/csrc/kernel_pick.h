@@ -1,0 +1,65 @@
+// Which instantiation of the path kernels a scene gets: the rules mi_render and mi_sample (csrc/miwave.hip) both follow, stated once.
+// Plain C++17 without HIP types, so that a host program can enumerate them (tests/test_kernel_pick.py).
+//
+// A rule maps the scene facts to (tiny, material class, analytic) = the leading template arguments of k_path_resident / k_sample_rays
+// (device/resident_kernel.h, device/sample_kernel.h), or to (class, analytic) of k_path_phased / k_path_pooled. The lists of tuples that
+// EXIST as instantiations live beside the launches in miwave.hip (MIW_*_LIST); a pick outside its list is an error there, never a default.
+// The order of the tests inside a rule is part of it: it also decides what combinations no scene has (lights_on without nested) get.
+#pragma once
+
+namespace miw_pick {
+
+// the material classes, by the values of miw/path.h's MATS_* (miwave.hip static_asserts the match)
+enum : int { ALL = 0, DIFFUSE = 1, PLAIN = 2, TRIO = 3, NESTED = 4, LIGHTS = 5 };
+
+struct Facts {
+    bool tiny;            // packet scene: LDS brute-force sweep instead of the tree (TraceLds::brute)
+    bool small;           // tri_count <= 32: 32-bit candidate masks
+    bool diffuse_only, trio, nested, textured, lights_on;   // mi_ctx, set by mi_scene_upload
+    bool no_rects;        // no analytic rectangles
+    bool trio_on;         // MIW_TRIO is not 0
+};
+
+struct Pick {
+    int tiny;             // 0: tree, 1: packets with 64-bit candidate masks, 2: with 32-bit masks
+    int mats;             // material class
+    bool analytic;        // analytic shapes compiled in
+};
+inline bool operator==(const Pick &a, const Pick &b) { return a.tiny == b.tiny && a.mats == b.mats && a.analytic == b.analytic; }
+
+// the MATS_TRIO class serves the scene (52 KB of code instead of MATS_PLAIN's 84)
+inline bool trio_kernel(const Facts &f) { return f.trio && f.trio_on && f.no_rects && !f.textured; }
+
+// resident path: k_path_resident<true, ..., INTEG_PATH> and the path side of k_sample_rays. The two differ in one line: mi_sample has a
+// MATS_TRIO tree kernel (with_trio), mi_render's lock-step tree kernel has none (its MATS_TRIO scenes run the phase machine).
+inline Pick resident_path(const Facts &f, bool with_trio) {
+    if (f.tiny && f.diffuse_only) return { f.small ? 2 : 1, DIFFUSE, false };   // no BSDF dispatch at all
+    if (f.lights_on) return { f.tiny ? 1 : 0, LIGHTS, !f.tiny };
+    if (f.nested) return { f.tiny ? 1 : 0, NESTED, !f.tiny };                   // + wrapper resolution, null / thindielectric
+    if (f.textured) return { f.tiny ? 1 : 0, ALL, !f.tiny };                    // texture coordinates / bitmap lookups compiled in
+    if (f.tiny) return { f.small ? 2 : 1, PLAIN, false };
+    if (with_trio && trio_kernel(f)) return { 0, TRIO, false };
+    return { 0, PLAIN, !f.no_rects };
+}
+
+// resident direct: k_path_resident<true, ..., INTEG_DIRECT> and the direct side of k_sample_rays
+inline Pick resident_direct(const Facts &f) {
+    const int mats = f.lights_on ? LIGHTS : f.nested ? NESTED : f.textured ? ALL : PLAIN;
+    return { f.tiny ? 1 : 0, mats, !f.tiny };
+}
+
+// the float64-atomics film (k_path_resident<false, ...>, path and direct alike): three classes, analytic shapes in every tree kernel
+inline Pick resident_atomic(const Facts &f) {
+    return { f.tiny ? 1 : 0, f.lights_on ? LIGHTS : f.nested ? NESTED : ALL, !f.tiny };
+}
+
+// tree class: k_path_phased and k_path_pooled (which refuses LIGHTS and NESTED)
+inline Pick tree_class(const Facts &f) {
+    if (f.lights_on) return { 0, LIGHTS, true };
+    if (f.nested) return { 0, NESTED, true };
+    if (f.textured) return { 0, ALL, true };
+    if (trio_kernel(f)) return { 0, TRIO, false };
+    return { 0, PLAIN, !f.no_rects };
+}
+
+}  // namespace miw_pick

@@ -1,5 +1,5 @@
 // libmiwave.so — gfx950 kernels and the C ABI declared in include/miwave.h. One translation unit (the build compiles the kernels of
-// one material class beside it, device/nested_instances.h):
+// two material classes beside it, device/class_instances.h):
 //   miw/*.h                      leaf arithmetic shared with the CPU checker (float32, fixed operation order)
 //   device/trace.h               LDS staging, packet sweep + leaf filter, LDS-stack BVH walk, trace2
 //   device/wavefront_kernels.h   plan 1: k_init_lanes, k_trace<closest|any>, k_shade over SoA queues in HBM
@@ -25,7 +25,8 @@
 #include <algorithm>
 
 #include "../../include/miwave.h"
-#if defined(MIW_NESTED_PART) || defined(MIW_LIGHTS_PART) || defined(MIW_AOV_UNIT)   /* miwave_nested.hip, miwave_lights.hip, miwave_aov.hip: the kernel headers alone */
+#include "kernel_pick.h"
+#if defined(MIW_CLASS_PART) || defined(MIW_AOV_UNIT)   /* miwave_class.hip, miwave_aov.hip: the kernel headers alone */
 #define MIW_KERNELS_ONLY 1
 #endif
 // Section clock (debug builds, -DMIW_SECTION_PROFILE=1): wall cycles per wavefront between markers, summed
@@ -60,7 +61,7 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "miw/bvh.h"
 #include "miw/path.h"
 #include "miw/direct.h"
-#if defined(MIW_KERNELS_ONLY)            /* miwave_nested.hip: the path kernels alone (device/nested_instances.h); the library's other kernels have one definition, here */
+#if defined(MIW_KERNELS_ONLY)            /* miwave_class.hip: the path kernels alone (device/class_instances.h); the library's other kernels have one definition, here */
 #include "miw/bvh4.h"
 #include "miw/bvh8.h"
 #define MIW_KERNEL static __global__    /* ... and those of their headers that are no templates stay out of its objects */
@@ -108,8 +109,7 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #endif
 #include "device/eval_kernels.h"
 #include "device/sample_kernel.h"
-#include "device/nested_instances.h"   /* a split build (-DMIW_SPLIT_NESTED=1) compiles the MATS_NESTED kernels in miwave_nested.hip */
-#include "device/lights_instances.h"   /* ... and (-DMIW_SPLIT_LIGHTS=1) the MATS_LIGHTS kernels in miwave_lights.hip */
+#include "device/class_instances.h"    /* a split build (-DMIW_SPLIT_CLASSES=1) compiles the MATS_NESTED and MATS_LIGHTS kernels in miwave_class.hip */
 #if defined(MIW_AOV_UNIT) || !defined(MIW_KERNELS_ONLY)
 #include "miw/aov.h"
 #include "miw/film_gather_n.h"
@@ -119,7 +119,7 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #endif
 #endif
 
-#if !defined(MIW_KERNELS_ONLY)           /* (miwave_nested.hip includes this file for the kernels above alone) */
+#if !defined(MIW_KERNELS_ONLY)           /* (miwave_class.hip includes this file for the kernels above alone) */
 __global__ void k_iota(uint32_t *out, uint32_t n) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = i; }
 
 // ---------------------------------------------------------------------------------------
@@ -205,6 +205,10 @@ struct Options {
     void from_env() { for (const KnobInfo &k : g_knobs) if (const char *e = getenv(k.name)) v[k.name] = e; }
     static bool known(const char *name) { for (const KnobInfo &k : g_knobs) if (!strcmp(k.name, name)) return true; return false; }
     const char *get(const char *name) const { auto it = v.find(name); return it == v.end() ? nullptr : it->second.c_str(); }
+    // a switch is off / on when it is SET and atoi of its value is 0 / not 0 (a value that is no number counts as 0); unset is neither: the default holds
+    bool off(const char *name) const { const char *e = get(name); return e && atoi(e) == 0; }
+    bool on(const char *name) const { const char *e = get(name); return e && atoi(e) != 0; }
+    int num(const char *name, int unset) const { const char *e = get(name); return e ? atoi(e) : unset; }
 };
 
 struct mi_ctx {
@@ -392,14 +396,14 @@ mi_status mi_film_reduce(mi_ctx *const *ctxs, void *const *films, int32_t n, uin
     // (one context: nothing to add — unless MIW_RCCL_FORCE=1 asks for the RCCL branch anyway: a communicator of one rank, an in-place
     // reduce that leaves the film as it is. That is how the branch — dlopen, ncclCommInitAll, the grouped ncclReduce, the stream
     // waits — runs on a one-GPU box: tests/test_multi_gpu.py)
-    const bool force_rccl = r->opt.get("MIW_RCCL_FORCE") && atoi(r->opt.get("MIW_RCCL_FORCE")) != 0;
+    const bool force_rccl = r->opt.on("MIW_RCCL_FORCE");
     if (count == 0 || (n == 1 && !force_rccl)) return MI_OK;
     std::vector<int> devs(n);
     bool distinct = true;
     for (int32_t i = 0; i < n; ++i) { devs[i] = ctxs[i]->device; for (int32_t j = 0; j < i; ++j) distinct = distinct && devs[j] != devs[i]; }
     if (distinct) {
         std::lock_guard<std::mutex> lock(g_rccl_mutex);
-        if (g_rccl.load(!(r->opt.get("MIW_RCCL") && atoi(r->opt.get("MIW_RCCL")) == 0))) {
+        if (g_rccl.load(!r->opt.off("MIW_RCCL"))) {
             auto it = g_rccl_comms.find(devs);
             if (it == g_rccl_comms.end()) {
                 std::vector<ncclComm_t> comms(n);
@@ -750,9 +754,9 @@ mi_status mi_bvh_build(mi_ctx *c, int32_t quality) {
     bool built_on_device = false;
     // quality 0: the 4-wide tree is collapsed on the device as well (bvh4_device.h); these say whether that happened
     bool wide_on_device = false; uint32_t dev4_nodes = 0, dev4_stack = 0;
-    const bool wide_on = !(c->opt.get("MIW_BVH4") && atoi(c->opt.get("MIW_BVH4")) == 0);
+    const bool wide_on = !c->opt.off("MIW_BVH4");
     // the 8-wide tree (the phase machine's default since round 5): off with MIW_BVH8=0, and whenever the 4-wide walk is asked for by name
-    const bool wide8_on = wide_on && !(c->opt.get("MIW_BVH8") && atoi(c->opt.get("MIW_BVH8")) == 0) && !c->opt.get("MIW_BVH4_FAN");
+    const bool wide8_on = wide_on && !c->opt.off("MIW_BVH8") && !c->opt.get("MIW_BVH4_FAN");
     uint32_t dev8_nodes = 0, dev8_depth = 0; double ms_bvh8 = 0.0;
     std::vector<uint32_t> sah_level_start;                    // the device SAH builder's level table (first node of every level)
     int max_fan = 4;
@@ -825,7 +829,7 @@ mi_status mi_bvh_build(mi_ctx *c, int32_t quality) {
             uint32_t n_cand = 1u, base = 0u, level = 0u;
             bool big_left = true;                                        // candidates of more than MIW_SAH_BIG triangles in the current level
             uint32_t level_max = un;                                     // the largest candidate of the current level (0: none above MIW_SAH_BIG)
-            const bool huge_on = !(c->opt.get("MIW_SAH_HUGE") && atoi(c->opt.get("MIW_SAH_HUGE")) == 0);     // MIW_SAH_HUGE=0: one workgroup per candidate, as round 4 (A/B runs)
+            const bool huge_on = !c->opt.off("MIW_SAH_HUGE");     // MIW_SAH_HUGE=0: one workgroup per candidate, as round 4 (A/B runs)
             while (n_cand > 0u && !sah_need_host) {
                 const SahCand *cur = (level & 1u) ? d_cb.p : d_ca.p; SahCand *nxt = (level & 1u) ? d_ca.p : d_cb.p;
                 const uint32_t *ic = (level & 1u) ? d_ib.p : d_ia.p; uint32_t *in = (level & 1u) ? d_ia.p : d_ib.p;
@@ -1284,6 +1288,51 @@ static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &
     return MI_OK;
 }
 
+// ---- which instantiation of the path kernels a scene gets ----------------------------------------------------------------------
+// kernel_pick.h holds the RULES (scene facts -> tiny, material class, analytic); the lists here hold every tuple that EXISTS as an instantiation,
+// once per kernel template. A launch matches its pick against its list (MIW_PICKED) and a pick outside the list is MI_ERR_STATE; nothing else
+// names these kernels with literal class arguments, but the special cases in front of the tables in mi_render (the overlap's Groups = true pair,
+// the four-wavefront shard kernel, the MATS_TRIO phase machine over the BVH2). A new class = a line in a rule + its tuples here (+ its
+// part lists in device/class_instances.h when it is compiled beside the library).
+static_assert(miw_pick::ALL == MATS_ALL && miw_pick::DIFFUSE == MATS_DIFFUSE && miw_pick::PLAIN == MATS_PLAIN && miw_pick::TRIO == MATS_TRIO &&
+              miw_pick::NESTED == MATS_NESTED && miw_pick::LIGHTS == MATS_LIGHTS, "kernel_pick.h names the classes by miw/path.h's values");
+// X(Tiny, Mats, Analytic, Integ): the sample-log film's k_path_resident<true, ...> (MIW_RESIDENT_LIST) and k_sample_rays (MIW_SAMPLE_LIST)
+#define MIW_PATH_TUPLES(X)                                                                                                              \
+    X(2, MATS_DIFFUSE, false, INTEG_PATH) X(1, MATS_DIFFUSE, false, INTEG_PATH)   /* 32-bit candidate masks up to 32 triangles (BASELINE config 2), else 64-bit */ \
+    X(1, MATS_LIGHTS, false, INTEG_PATH) X(0, MATS_LIGHTS, true, INTEG_PATH) X(1, MATS_NESTED, false, INTEG_PATH) X(0, MATS_NESTED, true, INTEG_PATH) \
+    X(1, MATS_ALL, false, INTEG_PATH) X(0, MATS_ALL, true, INTEG_PATH)                                                                  \
+    X(2, MATS_PLAIN, false, INTEG_PATH) X(1, MATS_PLAIN, false, INTEG_PATH) X(0, MATS_PLAIN, false, INTEG_PATH) X(0, MATS_PLAIN, true, INTEG_PATH)
+#define MIW_DIRECT_TUPLES(X)                                                                                                            \
+    X(1, MATS_LIGHTS, false, INTEG_DIRECT) X(0, MATS_LIGHTS, true, INTEG_DIRECT) X(1, MATS_NESTED, false, INTEG_DIRECT) X(0, MATS_NESTED, true, INTEG_DIRECT) \
+    X(1, MATS_ALL, false, INTEG_DIRECT) X(0, MATS_ALL, true, INTEG_DIRECT) X(1, MATS_PLAIN, false, INTEG_DIRECT) X(0, MATS_PLAIN, true, INTEG_DIRECT)
+#define MIW_RESIDENT_LIST(X) MIW_PATH_TUPLES(X) MIW_DIRECT_TUPLES(X)
+#define MIW_SAMPLE_LIST(X) MIW_PATH_TUPLES(X) X(0, MATS_TRIO, false, INTEG_PATH) MIW_DIRECT_TUPLES(X)
+// ... and the float64-atomics film's k_path_resident<false, ...> (launched, and given its LDS attribute, from this list)
+#define MIW_ATOMIC_LIST(X)                                                                                                              \
+    X(1, MATS_LIGHTS, false, INTEG_PATH) X(0, MATS_LIGHTS, true, INTEG_PATH) X(1, MATS_NESTED, false, INTEG_PATH) X(0, MATS_NESTED, true, INTEG_PATH) \
+    X(1, MATS_ALL, false, INTEG_PATH) X(0, MATS_ALL, true, INTEG_PATH)                                                                  \
+    X(1, MATS_LIGHTS, false, INTEG_DIRECT) X(0, MATS_LIGHTS, true, INTEG_DIRECT) X(1, MATS_NESTED, false, INTEG_DIRECT) X(0, MATS_NESTED, true, INTEG_DIRECT) \
+    X(1, MATS_ALL, false, INTEG_DIRECT) X(0, MATS_ALL, true, INTEG_DIRECT)
+// X(Mats, Analytic, Waves, Wide, Placed): k_path_phased — the six tree classes, each over the 8-wide and the 4-wide tree at four wavefronts per
+// SIMD, placed or not, and over the 4-wide tree at three
+#define MIW_TREE_CLASSES(X, ...) X(MATS_LIGHTS, true, __VA_ARGS__) X(MATS_NESTED, true, __VA_ARGS__) X(MATS_ALL, true, __VA_ARGS__) \
+    X(MATS_TRIO, false, __VA_ARGS__) X(MATS_PLAIN, false, __VA_ARGS__) X(MATS_PLAIN, true, __VA_ARGS__)
+#define MIW_PHASED_LIST(X) MIW_TREE_CLASSES(X, 4, 2, true) MIW_TREE_CLASSES(X, 4, 2, false) MIW_TREE_CLASSES(X, 4, 1, true) MIW_TREE_CLASSES(X, 4, 1, false) MIW_TREE_CLASSES(X, 3, 1, false)
+// X(Mats, Analytic, NW, PP): k_path_pooled (the 8 x 2 shape is instantiated for the MATS_TRIO class only — BASELINE configs 3 / 4)
+#define MIW_POOLED_LIST(X) X(MATS_ALL, true, 12, 1) X(MATS_TRIO, false, 12, 1) X(MATS_TRIO, false, 8, 2) X(MATS_PLAIN, false, 12, 1) X(MATS_PLAIN, true, 12, 1)
+#define MIW_PICKED(T, M, A) (pick.tiny == (T) && pick.mats == (M) && pick.analytic == (A))
+
+// the scene facts the rules read, from the context and the options of this call
+static miw_pick::Facts pick_facts(const mi_ctx *c, const Options &opt) {
+    miw_pick::Facts f;
+    f.tiny = c->lds_cfg.brute != 0; f.small = c->view.tri_count <= 32u;
+    f.diffuse_only = c->diffuse_only; f.trio = c->trio; f.nested = c->nested; f.textured = c->textured; f.lights_on = c->lights_on;
+    f.no_rects = c->rects.empty(); f.trio_on = !opt.off("MIW_TRIO");
+    return f;
+}
+// the 8-wide tree is there and not switched off (MIW_BVH8=0 keeps the 4-wide walk: A/B runs in one process)
+static bool tree8_on(const mi_ctx *c, const Options &opt) { return c->view.nodes4 != nullptr && c->nodes8_count != 0u && !opt.off("MIW_BVH8"); }
+
 // ---- mi_sample: SamplingIntegrator::sample for caller-supplied rays (device/sample_kernel.h) ------------------------------
 // Rays per launch. Host-pointer calls stage one chunk at a time in a buffer the context keeps (88 + 4 N bytes per ray: 200 MB),
 // so n is bounded by the caller's memory only; device-pointer calls are cut as well, so that mi_cancel is looked at in between
@@ -1291,39 +1340,18 @@ static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &
 #define MIW_SAMPLE_CHUNK_HOST (1u << 21)
 #define MIW_SAMPLE_CHUNK_DEVICE (1u << 26)
 static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO &io, hipStream_t s) {
-    const bool tiny = c->lds_cfg.brute != 0, direct = P.integrator == INTEG_DIRECT, small = c->view.tri_count <= 32u;
-    const bool trio_on = !(c->opt.get("MIW_TRIO") && atoi(c->opt.get("MIW_TRIO")) == 0);
-    const bool trio_kernel = c->trio && trio_on && c->rects.empty() && !c->textured;
+    const bool tiny = c->lds_cfg.brute != 0, direct = P.integrator == INTEG_DIRECT;
     // persistent grid: as many workgroups per CU as the kernel is compiled for wavefronts per SIMD (sample_kernel.h), never more than the rays need
     const unsigned waves = direct ? (unsigned) MIW_DIRECT_WAVES : tiny ? 4u : (unsigned) MIW_TREE_WAVES;
     const dim3 grid(std::min<unsigned>((io.n + MIW_BLOCK - 1u) / MIW_BLOCK, (unsigned) c->cu_count * waves)), block(MIW_BLOCK);
     HIP_TRY(c, hipMemsetAsync(c->d_next_ray.p, 0, sizeof(uint32_t), s));
-#define MIW_SAMPLE_LAUNCH(T, M, A, I) hipLaunchKernelGGL((k_sample_rays<T, M, A, I>), grid, block, c->lds_bytes, s, P, c->view, io, c->lds_cfg, c->d_next_ray.p)
-    // the instantiation mi_render would pick for this scene: no BSDF dispatch when every shape is plain diffuse, no texture lookups
-    // without texture coordinates, no analytic shapes where there are none
-    if (direct) {
-        if (tiny && c->lights_on) MIW_SAMPLE_LAUNCH(1, MATS_LIGHTS, false, INTEG_DIRECT);
-        else if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_DIRECT);
-        else if (c->lights_on) MIW_SAMPLE_LAUNCH(0, MATS_LIGHTS, true, INTEG_DIRECT);
-        else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_DIRECT);
-        else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_DIRECT);
-        else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_DIRECT);
-        else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_DIRECT);
-        else MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, true, INTEG_DIRECT);
-    }
-    else if (tiny && c->diffuse_only && small) MIW_SAMPLE_LAUNCH(2, MATS_DIFFUSE, false, INTEG_PATH);
-    else if (tiny && c->diffuse_only) MIW_SAMPLE_LAUNCH(1, MATS_DIFFUSE, false, INTEG_PATH);
-    else if (tiny && c->lights_on) MIW_SAMPLE_LAUNCH(1, MATS_LIGHTS, false, INTEG_PATH);
-    else if (tiny && c->nested) MIW_SAMPLE_LAUNCH(1, MATS_NESTED, false, INTEG_PATH);
-    else if (c->lights_on) MIW_SAMPLE_LAUNCH(0, MATS_LIGHTS, true, INTEG_PATH);
-    else if (c->nested) MIW_SAMPLE_LAUNCH(0, MATS_NESTED, true, INTEG_PATH);
-    else if (tiny && c->textured) MIW_SAMPLE_LAUNCH(1, MATS_ALL, false, INTEG_PATH);
-    else if (c->textured) MIW_SAMPLE_LAUNCH(0, MATS_ALL, true, INTEG_PATH);
-    else if (tiny && small) MIW_SAMPLE_LAUNCH(2, MATS_PLAIN, false, INTEG_PATH);
-    else if (tiny) MIW_SAMPLE_LAUNCH(1, MATS_PLAIN, false, INTEG_PATH);
-    else if (trio_kernel) MIW_SAMPLE_LAUNCH(0, MATS_TRIO, false, INTEG_PATH);
-    else if (c->rects.empty()) MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, false, INTEG_PATH);
-    else MIW_SAMPLE_LAUNCH(0, MATS_PLAIN, true, INTEG_PATH);
+    // the instantiation mi_render picks for this scene (the same rule: no BSDF dispatch when every shape is plain diffuse, no texture lookups
+    // without texture coordinates, no analytic shapes where there are none), plus the MATS_TRIO tree kernel mi_render leaves to its phase machine
+    const miw_pick::Facts facts = pick_facts(c, c->opt);
+    const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, true);
+    const uint32_t integ = direct ? INTEG_DIRECT : INTEG_PATH;
+#define MIW_SAMPLE_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) hipLaunchKernelGGL((k_sample_rays<T, M, A, I>), grid, block, c->lds_bytes, s, P, c->view, io, c->lds_cfg, c->d_next_ray.p); else
+    MIW_SAMPLE_LIST(MIW_SAMPLE_LAUNCH) return fail(c, MI_ERR_STATE, "mi_sample: no k_sample_rays<%d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_SAMPLE_LAUNCH
     HIP_TRY(c, hipGetLastError());
     return MI_OK;
@@ -1690,20 +1718,17 @@ static mi_status overlap_enqueue(mi_ctx *c, const Options &ropt, const RenderPar
     // wavefront's chain (~8 - 10 ms) however little it is; measured at C2 (gpurun r6m): three quarters beside 263.6 ms, half 266.1, none 265.8
     uint32_t n_groups = n_all * 3u / 4u;
     if (const char *e = ropt.get("MIW_FILM_OVERLAP_BESIDE")) n_groups = (uint32_t) std::min<long>(std::max<long>(atol(e), 0), (long) n_all);
-    int prio = 0;
-    if (const char *e = ropt.get("MIW_FILM_OVERLAP_PRIO")) prio = std::min(3, std::max(0, atoi(e)));
+    const int prio = std::min(3, std::max(0, ropt.num("MIW_FILM_OVERLAP_PRIO", 0)));
     PatchArgs PC; PC.patches_x = PC.patches_y = (R.side + MIW_FL_BS - 1) / MIW_FL_BS; PC.reach = c->classes.reach;
     const uint32_t n_pos = PC.patches_x * PC.patches_y;
     const size_t lbytes = (size_t) (c->classes.count + 1u) * MIW_FQ_WSTRIDE(MIW_FL_BS) * sizeof(float);
-    int fl_nt = 1;
-    if (const char *e = ropt.get("MIW_FL_NT")) fl_nt = atoi(e);
+    const int fl_nt = ropt.num("MIW_FL_NT", 1);
     // One launch replays a SET of groups (MIW_FILM_OVERLAP_SET, default 4: 324 wavefronts) behind the flags of all of them; the sets go round the three
     // replay streams — kernels of one stream run one after the other, and a replay kernel lasts as long as ONE of its wavefronts (64 pixel runs, a
     // serial chain of ~4 ms) however few there are: one launch per group on one stream would be a chain of 32 such kernels.
     uint32_t set = 4u;
     if (const char *e = ropt.get("MIW_FILM_OVERLAP_SET")) set = (uint32_t) std::max(1, atoi(e));
-    bool lean_ok = fl_nt != 0;
-    if (const char *e = ropt.get("MIW_FILM_OVERLAP_LEAN")) lean_ok = lean_ok && atoi(e) != 0;
+    const bool lean_ok = fl_nt != 0 && !ropt.off("MIW_FILM_OVERLAP_LEAN");
     for (int i = 0; i < 3; ++i) HIP_TRY(c, hipStreamWaitEvent(c->stream2[i], c->ev_fork, 0));
     uint32_t launches = 0;
     for (uint32_t g0 = 0; g0 < n_groups; g0 += set, ++launches) {
@@ -1780,8 +1805,7 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
                     // 16-byte class records -> per-group pixel lists (k_film_groups). Group shape: 2x2 reads 6.25 sample rows per texel,
                     // 4x4 3.06 but spends 0.77 wave-iterations per sample; 4x2 (4.4 rows, 0.55) balances HBM reads against issue slots.
                     // MIW_FILM_GROUP = 2 | 3 | 4 overrides (2x2 / 4x2 / 4x4).
-                    int group = 3;
-                    if (const char *e = ropt.get("MIW_FILM_GROUP")) group = atoi(e);
+                    const int group = ropt.num("MIW_FILM_GROUP", 3);
                     const size_t wbytes = (size_t) (c->classes.count + 1u) * MIW_FG_WSTRIDE * sizeof(float);
 #define MIW_FG_LAUNCH(GW, GH) MIW_TIMED(4, hipLaunchKernelGGL((k_film_groups<GW, GH>), fgrid, dim3(64), wbytes, s, P.film, A, PA, c->d_tiles.p))
                     // round 4: a column of GH texels per lane (k_film_columns; MIW_FILM_COLUMNS = 0: the one-texel-per-lane kernel, 42 / 44: 4 x 2 / 4 x 4 groups;
@@ -1792,8 +1816,7 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
                     // round 5: groups of 4 x 2 (2 x 4: MIW_FILM_QUADS = 24) texels inside DPP quads, the records broadcast by quad_perm operands instead of
                     // staged through LDS (k_film_quads; MIW_FILM_QUADS = 24 / 28 / 44: other group shapes, = 0: the kernels below — also taken when a tile
                     // has fewer groups than a wavefront takes, i.e. tiny blocks)
-                    int columns = 42;
-                    if (const char *e = ropt.get("MIW_FILM_COLUMNS")) columns = atoi(e);
+                    const int columns = ropt.num("MIW_FILM_COLUMNS", 42);
                     // (what runs here by default are shards of fewer than 448 tiles — k_film_lanes takes the rest —: 4 x 2 groups, twice as many and half as
                     // long wavefronts as 2 x 4: a rank's eighth of a 1080p frame 3.63 ms against 4.13, k_film_columns 4.19, gpurun q11; a whole frame 24.1 / 23.8)
                     int quads = ropt.get("MIW_FILM_COLUMNS") == nullptr && ropt.get("MIW_FILM_GROUP") == nullptr ? 42 : 0;
@@ -1808,8 +1831,7 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
                     if (lanes) {
                         PatchArgs PC = PA; PC.patches_x = PC.patches_y = (side + MIW_FL_BS - 1) / MIW_FL_BS;
                         const size_t lbytes = (size_t) (c->classes.count + 1u) * MIW_FQ_WSTRIDE(MIW_FL_BS) * sizeof(float);
-                        int fl_nt = 1;                                    // the log read with streaming loads (16.8 vs 17.05 ms at C2, gpurun q9); MIW_FL_NT = 0: plain loads
-                        if (const char *e = ropt.get("MIW_FL_NT")) fl_nt = atoi(e);
+                        const int fl_nt = ropt.num("MIW_FL_NT", 1);       // the log read with streaming loads (16.8 vs 17.05 ms at C2); MIW_FL_NT = 0: plain loads
                         // (the groups of 64 tiles below `first` were replayed beside the path kernel, on the replay streams: overlap_enqueue)
                         const uint32_t first = queued ? queued->beside : 0u, groups_all = ((uint32_t) n_tiles + 63u) / 64u;
                         const uint32_t waves_rest = (groups_all - first) * PC.patches_x * PC.patches_y;
@@ -1822,8 +1844,7 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
                         const uint32_t per_wave = 64u / qw, waves = (uint32_t) (((size_t) n_tiles * PC.patches_x * PC.patches_y + per_wave - 1u) / per_wave);
                         const size_t qbytes = (size_t) (c->classes.count + 1u) * (size_t) (5u + 2u * qh) * sizeof(float);
 #define MIW_FQ_LAUNCH(GW, GH, U) MIW_TIMED(4, hipLaunchKernelGGL((k_film_quads<GW, GH, U>), dim3(waves), dim3(64), qbytes, s, P.film, A, PC, (uint32_t) n_tiles, c->d_tiles.p))
-                        int fq_u = 4;
-                        if (const char *e = ropt.get("MIW_FQ_U")) fq_u = atoi(e);
+                        const int fq_u = ropt.num("MIW_FQ_U", 4);
                         if (quads == 24) { if (fq_u == 8) MIW_FQ_LAUNCH(2, 4, 8); else if (fq_u == 2) MIW_FQ_LAUNCH(2, 4, 2); else MIW_FQ_LAUNCH(2, 4, 4); }
                         else if (quads == 42) { if (fq_u == 8) MIW_FQ_LAUNCH(4, 2, 8); else MIW_FQ_LAUNCH(4, 2, 4); }
                         else if (quads == 28) MIW_FQ_LAUNCH(2, 8, 4); else MIW_FQ_LAUNCH(4, 4, 4);
@@ -1873,7 +1894,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         case MI_FILM_REPLAY_BLOCKS: ropt.v["MIW_FILM_LEGACY"] = "1"; break;
         case MI_FILM_REPLAY_GROUPS: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "0"; ropt.v["MIW_FILM_QUADS"] = "0"; ropt.v["MIW_FILM_COLUMNS"] = "0"; break;
         case MI_FILM_REPLAY_COLUMNS: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "0"; ropt.v["MIW_FILM_QUADS"] = "0"; ropt.v.erase("MIW_FILM_COLUMNS"); ropt.v.erase("MIW_FILM_GROUP"); break;
-        case MI_FILM_REPLAY_QUADS: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "0"; ropt.v.erase("MIW_FILM_COLUMNS"); ropt.v.erase("MIW_FILM_GROUP"); if (ropt.get("MIW_FILM_QUADS") && atoi(ropt.get("MIW_FILM_QUADS")) == 0) ropt.v.erase("MIW_FILM_QUADS"); break;
+        case MI_FILM_REPLAY_QUADS: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "0"; ropt.v.erase("MIW_FILM_COLUMNS"); ropt.v.erase("MIW_FILM_GROUP"); if (ropt.off("MIW_FILM_QUADS")) ropt.v.erase("MIW_FILM_QUADS"); break;
         case MI_FILM_REPLAY_LANES: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "1"; break;
         case MI_FILM_REPLAY_LANES_PLAIN_LOG: ropt.v.erase("MIW_FILM_LEGACY"); ropt.v["MIW_FILM_LANES"] = "2"; break;
         default: return fail(c, MI_ERR_INVALID, "render: debug_film_replay must be one of MI_FILM_REPLAY_*");
@@ -1925,6 +1946,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     plan = 2;
 #endif
     const bool direct = P.integrator == INTEG_DIRECT;
+    const uint32_t integ = direct ? INTEG_DIRECT : INTEG_PATH;
     if (direct) {                                                // direct.h runs on the paired query of the resident plan
         if (cfg->plan == 1) return fail(c, MI_ERR_INVALID, "render: the direct integrator runs the resident plan only (plan 0 or 2)");
         plan = 2;
@@ -1981,7 +2003,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // what lds_workgroups() below allows)
         L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u - MIW_LDS_STATIC - MIW_LDS_GRANULE : lds_budget);
         L.cfg.env_top_count = L.cfg.env_top_base = L.cfg.env_top_words = 0;
-        if (L.tables_fit && c->have_env && !(ropt.get("MIW_ENV_TOP") && atoi(ropt.get("MIW_ENV_TOP")) == 0)) {
+        if (L.tables_fit && c->have_env && !ropt.off("MIW_ENV_TOP")) {
             // ... and as many of the environment warp's smallest levels as fit what is left (at most env_cap): levels are stored from
             // the largest (0) to the smallest (n_levels - 1), so the top `count` levels are the tail of the array
             const EnvmapRec &e = c->env_host;
@@ -2003,11 +2025,11 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     };
     LdsLayout lay = lay_out(c->lds_bytes, 4096, lds_budget4);
     // will this render walk the 8-wide tree? (the conditions mi_render applies below, known here already; MIW_BVH8=0 keeps the 4-wide walk)
-    const bool pre8 = plan == 2 && cfg->integrator != MI_INTEGRATOR_DIRECT && !c->lds_cfg.brute && c->lds_cfg.stack && c->view.nodes4 && c->nodes8_count != 0u &&
-                      !(ropt.get("MIW_BVH8") && atoi(ropt.get("MIW_BVH8")) == 0) && !(ropt.get("MIW_PHASED") && atoi(ropt.get("MIW_PHASED")) == 0) &&
-                      !(ropt.get("MIW_PHASED_WAVES") && atoi(ropt.get("MIW_PHASED_WAVES")) != 4) && film_mode == 1;
+    const miw_pick::Facts facts = pick_facts(c, ropt);          // what the kernel-class rules read (kernel_pick.h)
+    const bool pre8 = plan == 2 && cfg->integrator != MI_INTEGRATOR_DIRECT && !c->lds_cfg.brute && c->lds_cfg.stack && tree8_on(c, ropt) &&
+                      !ropt.off("MIW_PHASED") && ropt.num("MIW_PHASED_WAVES", 4) == 4 && film_mode == 1;
     bool stack8_sized = false;
-    if (pre8 && !(ropt.get("MIW_STACK8_FULL") && atoi(ropt.get("MIW_STACK8_FULL")) != 0)) {
+    if (pre8 && !ropt.on("MIW_STACK8_FULL")) {
         const size_t base8 = (size_t) c->lds_cfg.stack16 * 16 + (size_t) std::max<uint32_t>(c->nodes8_depth, 2u) * MIW_BLOCK * sizeof(U2);
         const LdsLayout lay8 = lay_out(base8, 12288, lds_budget4);
         if (lay8.tables_fit && base8 <= c->lds_bytes) { lay = lay8; stack8_sized = true; }
@@ -2022,8 +2044,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     int pool_nw = 12, pool_pp = 1;
     if (const char *e = ropt.get("MIW_POOL_SHAPE")) { int a = 0, b = 0; if (sscanf(e, "%dx%d", &a, &b) == 2 && ((a == 12 && b == 1) || (a == 8 && b == 2))) { pool_nw = a; pool_pp = b; } }
     // (the 8 x 2 shape is instantiated for the MATS_TRIO class only — BASELINE configs 3 / 4)
-    if (!(c->trio && !(ropt.get("MIW_TRIO") && atoi(ropt.get("MIW_TRIO")) == 0) && c->rects.empty() && !c->textured)) { pool_nw = 12; pool_pp = 1; }
-    if (pre8 && ropt.get("MIW_POOLED") && atoi(ropt.get("MIW_POOLED")) != 0) {
+    if (!miw_pick::trio_kernel(facts)) { pool_nw = 12; pool_pp = 1; }
+    if (pre8 && ropt.on("MIW_POOLED")) {
         const size_t NJ = (size_t) pool_nw * pool_pp * 64u;
         size_t base = (size_t) std::max<uint32_t>(c->nodes8_depth, 2u) * NJ * sizeof(U2);
         const uint32_t pool16 = (uint32_t) (base / 16); base += 5u * NJ * 16u;
@@ -2093,17 +2115,15 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // for the plain-diffuse packet kernel, 3 for the others — a shard larger than that is balanced by the queue itself)
         // Which path kernel runs (decided here because placement depends on it): tree scenes with the LDS-stack walk get the wave-level
         // phase machine (device/phased_kernel.h; MIW_PHASED=0 keeps the lock-step kernel, MIW_TRIO=0 the full BSDF table: A/B runs)
-        const bool tiny = c->lds_cfg.brute != 0;
-        const bool phased_on = !(ropt.get("MIW_PHASED") && atoi(ropt.get("MIW_PHASED")) == 0);
-        const bool trio_on = !(ropt.get("MIW_TRIO") && atoi(ropt.get("MIW_TRIO")) == 0);
-        const bool trio_kernel = c->trio && trio_on && c->rects.empty() && !c->textured;   // 52 KB of code instead of 84
+        const bool tiny = facts.tiny;
+        const bool phased_on = !ropt.off("MIW_PHASED");
+        const bool trio_kernel = miw_pick::trio_kernel(facts);
         const bool phased = phased_on && !direct && !tiny && c->lds_cfg.stack && (c->view.nodes4 != nullptr || trio_kernel) && (tables_fit || !MIW_LDS_TABLES);
         // 4 waves per SIMD for every tree (measured: 0.9 M triangles +7 - 11 %, 41 k triangles +-0 before the register diet, +8 % after); MIW_PHASED_WAVES = 3 | 4 overrides
-        int ph_waves = 4;
-        if (const char *e = ropt.get("MIW_PHASED_WAVES")) ph_waves = atoi(e) == 4 ? 4 : 3;
+        const int ph_waves = ropt.num("MIW_PHASED_WAVES", 4) == 4 ? 4 : 3;
         const bool phased_placeable = phased && c->view.nodes4 != nullptr && ph_waves == 4;     // (the Placed instantiations: the 4-wide tree at four waves per SIMD)
         // the 8-wide tree whenever mi_bvh_build produced one (four waves per SIMD only; MIW_BVH8=0 here keeps the 4-wide walk: A/B runs in one process)
-        const bool phased8 = phased_placeable && c->nodes8_count != 0u && !(ropt.get("MIW_BVH8") && atoi(ropt.get("MIW_BVH8")) == 0);
+        const bool phased8 = phased_placeable && tree8_on(c, ropt);
         if (stack8_sized && !phased8) return fail(c, MI_ERR_STATE, "render: the LDS stack was sized for the 8-wide walk, which this launch does not run");
         SceneView view8 = c->view;
         if (phased8) { view8.nodes8 = c->d_nodes8.p; view8.tris = c->d_tris8.p; if (view8.tri_vn) view8.tri_vn = c->d_tri_vn8.p; }
@@ -2111,16 +2131,15 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // (the plain-diffuse packet kernel of <= 32 triangles: five — or, when the job's pixels fill no more than four wavefronts per SIMD (a rank's shard), the
         // 128-register instantiation for four: resident_kernel.h; MIW_PACKET_SHARD4=0 keeps five)
         bool packet_shard4 = !phased && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct && c->view.tri_count <= 32u && MIW_PACKET_WAVES > 4 && film_mode == 1 && n_lanes <= 64u * 4u * n_simd;
-        if (const char *e = ropt.get("MIW_PACKET_SHARD4")) packet_shard4 = packet_shard4 && atoi(e) != 0;
+        if (ropt.off("MIW_PACKET_SHARD4")) packet_shard4 = false;
         const uint32_t res_waves_compiled = phased ? (uint32_t) ph_waves : !tiny ? (uint32_t) MIW_TREE_WAVES : (c->diffuse_only && !MIW_SPECTRAL ? (c->view.tri_count <= 32u && !packet_shard4 ? (uint32_t) MIW_PACKET_WAVES : 4u) : (uint32_t) MIW_PACKET_WAVES_ALL);
         // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
         // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
         const uint32_t res_waves = tiny && film_mode == 1 ? std::max(1u, std::min(res_waves_compiled, lds_workgroups(rlds))) : res_waves_compiled;
         bool place = film_mode == 1 && !direct && (tiny || phased_placeable) && n_lanes >= 64u * n_simd / 2u && n_lanes <= 64u * res_waves * n_simd &&
                      cfg->spp >= 128u && per_launch >= cfg->spp && cfg->timeout_s <= 0.f;
-        if (const char *e = ropt.get("MIW_PLACE")) place = place && atoi(e) != 0;
-        uint32_t measure_div = 8u;                                 // the measuring launch runs spp / 8 samples (MIW_PLACE_MEASURE = divisor)
-        if (const char *e = ropt.get("MIW_PLACE_MEASURE")) measure_div = (uint32_t) std::max(2, atoi(e));
+        if (ropt.off("MIW_PLACE")) place = false;
+        uint32_t measure_div = (uint32_t) std::max(2, ropt.num("MIW_PLACE_MEASURE", 8));                                 // the measuring launch runs spp / 8 samples (MIW_PLACE_MEASURE = divisor)
         const uint32_t measure_end = place ? std::max<uint32_t>(16u, cfg->spp / measure_div) : 0u;
         const uint32_t n_pieces = (n_lanes + 63u) / 64u;
         size_t place_tmp_bytes = 0;
@@ -2144,18 +2163,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
             TA.geom16 = (uint32_t) ((c->lds_bytes + 15) / 16);
             tile_bytes = (size_t) TA.geom16 * 16 - c->lds_bytes + (size_t) TA.side * TA.side * MIW_FILM_CHANNELS * sizeof(double);
             if (c->lds_bytes + tile_bytes > 64 * 1024) {
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_ALL, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_ALL, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_LIGHTS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_LIGHTS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 1, MATS_LIGHTS, false, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, 0, MATS_LIGHTS, true, INTEG_DIRECT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+#define MIW_ATOMIC_ATTR(T, M, A, I) HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, T, M, A, I>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
+                MIW_ATOMIC_LIST(MIW_ATOMIC_ATTR)
+#undef MIW_ATOMIC_ATTR
             }
         }
         const uint32_t sync_every = 8;
@@ -2166,8 +2176,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // OPT-IN (MIW_FILM_OVERLAP=1): measured at C2 (gpurun r6k - r6m, profiles/r06_experiments.txt) it hides up to 3/4 of the replay and gains 0 - 1 % of the
         // frame — the wave slots it needs cost the path kernel in proportion (32 workgroups short: +6 ms), a replay wavefront beside three packet-kernel
         // wavefronts takes 20 - 30 ms instead of 5, and what is left after the path kernel cannot take less than one wavefront's chain (~8 - 10 ms)
-        int overlap_mode = 0;
-        if (const char *e = ropt.get("MIW_FILM_OVERLAP")) overlap_mode = atoi(e);
+        const int overlap_mode = ropt.num("MIW_FILM_OVERLAP", 0);
         const bool overlap = overlap_mode != 0 && c->overlap_state != 0 && film_mode == 1 && FP.rec16 && FP.film_lanes != 0 && FP.log_il != 0 && !place && !phased /* (QueueWork<..., Groups = false>) */ && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct /* the 120-register packet kernel: the only one a replay wavefront fits beside */ &&
                              per_launch >= cfg->spp && cfg->timeout_s <= 0.f && n_tiles > 0;
         for (uint32_t done = 0; done < cfg->spp; ) {
@@ -2196,7 +2205,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     // from 1.2 pixels per resident lane on (gpurun r6z, a rank's shard of C2 with / without: 4 ranks = 1.6 pixels per lane 67.8 / 79.1 ms, 5 ranks = 1.3: 58.7 / 67.5,
                     // 6 ranks = 1.06: 54.9 / 54.6; at about ONE pixel per lane every pixel is in flight all the time and no lane finds a second job: 8 ranks 47.1 against the placed launches' 41.4)
                     bool enough = (uint64_t) n_lanes * 5u >= (uint64_t) 6u * 64u * res_waves * n_simd;
-                    if (const char *e = ropt.get("MIW_JOB_CHUNK_FORCE")) enough = enough || atoi(e) != 0;
+                    if (ropt.on("MIW_JOB_CHUNK_FORCE")) enough = true;
                     uint32_t pow2 = 1u;
                     while (pow2 * 2u < cfg->spp) pow2 *= 2u;                          // the largest power of two below spp
                     uint64_t chunks = 1u;
@@ -2264,9 +2273,6 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 const unsigned resident = (unsigned) c->cu_count * (direct ? (unsigned) MIW_DIRECT_WAVES : (unsigned) res_waves);
                 const unsigned full = room ? std::min((unsigned) c->cu_count * wg_per_cu, resident) : (unsigned) c->cu_count * wg_per_cu;
                 const dim3 pgrid(std::min<unsigned>(grid.x, full > 2u * room ? full - room : full));
-#define MIW_PATH_LAUNCH(T, M) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
-                // kernel variants: no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that
-                // variant fits 4 waves per SIMD without spills); else 32-bit candidate masks up to 32 triangles
                 // (`phased`, `trio_kernel`, `ph_waves`: decided above the loop; MIW_BVH4=0 keeps the BVH2 node body for the MATS_TRIO class: A/B runs)
                 K.path_kernel = phased ? (c->view.nodes4 ? 1u : 3u) : 0u;
                 const dim3 phgrid(std::min<unsigned>(grid.x, (unsigned) c->cu_count * (unsigned) ph_waves));
@@ -2282,7 +2288,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 // 42.3 ms; 1/8 of the material balls -14 %), it also shortens the drain of a full frame (C2 275.9 -> 268.7 ms), so it is
                 // always on. MIW_TAIL_PRIO = 0 | 1 overrides.
                 rcfg.tail_prio = 1u;
-                if (const char *e = ropt.get("MIW_TAIL_PRIO")) rcfg.tail_prio = atoi(e) ? 1u : 0u;
+                if (ropt.off("MIW_TAIL_PRIO")) rcfg.tail_prio = 0u;
                 TraceLds ph_cfg = rcfg;
                 ph_cfg.shade_num = 2; ph_cfg.shade_den = c->have_env ? 4 : 3;
                 if (const char *e = ropt.get("MIW_SHADE_VOTE")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0) { ph_cfg.shade_num = (uint32_t) a; ph_cfg.shade_den = (uint32_t) b; } }
@@ -2310,108 +2316,51 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     const unsigned NL = (unsigned) pool_nw * 64u;
                     const dim3 qgrid(std::min<unsigned>((n_lanes + NL - 1u) / NL, (unsigned) c->cu_count)), qblock(NL);
                     SceneView pview = view8;
-#define MIW_POOLED_LAUNCH_(M, A, NW_, PP_) do { HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
-                                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } while (0)
-#define MIW_POOLED_LAUNCH(M, A) do { if (pool_pp == 2) MIW_POOLED_LAUNCH_(M, A, 8, 2); else MIW_POOLED_LAUNCH_(M, A, 12, 1); } while (0)
                     if (c->lights_on) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with point / spot / directional / constant emitters");
-                    else if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
-                    else if (c->textured) MIW_POOLED_LAUNCH_(MATS_ALL, true, 12, 1);
-                    else if (trio_kernel) MIW_POOLED_LAUNCH(MATS_TRIO, false);
-                    else if (c->rects.empty()) MIW_POOLED_LAUNCH_(MATS_PLAIN, false, 12, 1);
-                    else MIW_POOLED_LAUNCH_(MATS_PLAIN, true, 12, 1);
+                    if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
+                    const miw_pick::Pick pick = miw_pick::tree_class(facts);
+#define MIW_POOLED_LAUNCH(M, A, NW_, PP_) if (pick.mats == (M) && pick.analytic == (A) && pool_nw == (NW_) && pool_pp == (PP_)) { \
+                        HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
+                        MIW_TIMED(6, hipLaunchKernelGGL((k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } else
+                    MIW_POOLED_LIST(MIW_POOLED_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_pooled<%d, %d, %d, %d> in the library", pick.mats, (int) pick.analytic, pool_nw, pool_pp);
 #undef MIW_POOLED_LAUNCH
-#undef MIW_POOLED_LAUNCH_
                     K.pooled = 1u; K.pool_waves = (uint32_t) pool_nw;
                 }
 #endif
                 else
-                if (phased8 && place) {
-                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 2, true);
-                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, true);
-                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, true);
-                    else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, true);
-                    else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, true);
-                    else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, true);
-                } else if (phased8) {
-                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 2, false);
-                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 2, false);
-                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 2, false);
-                    else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 2, false);
-                    else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 2, false);
-                    else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 2, false);
-                } else if (phased && place) {                           // a shard of about one pixel per resident lane: the Placed instantiations (measuring, then placed launch)
-                    if (c->lights_on) MIW_PHASED_LAUNCH_(MATS_LIGHTS, true, 4, 1, true);
-                    else if (c->nested) MIW_PHASED_LAUNCH_(MATS_NESTED, true, 4, 1, true);
-                    else if (c->textured) MIW_PHASED_LAUNCH_(MATS_ALL, true, 4, 1, true);
-                    else if (trio_kernel) MIW_PHASED_LAUNCH_(MATS_TRIO, false, 4, 1, true);
-                    else if (c->rects.empty()) MIW_PHASED_LAUNCH_(MATS_PLAIN, false, 4, 1, true);
-                    else MIW_PHASED_LAUNCH_(MATS_PLAIN, true, 4, 1, true);
-                } else if (phased) {
-                    if (!c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);
-                    else if (c->lights_on) MIW_PHASED_LAUNCH(MATS_LIGHTS, true, 1);
-                    else if (c->nested) MIW_PHASED_LAUNCH(MATS_NESTED, true, 1);
-                    else if (c->textured) MIW_PHASED_LAUNCH(MATS_ALL, true, 1);
-                    else if (trio_kernel) MIW_PHASED_LAUNCH(MATS_TRIO, false, 1);
-                    else if (c->rects.empty()) MIW_PHASED_LAUNCH(MATS_PLAIN, false, 1);
-                    else MIW_PHASED_LAUNCH(MATS_PLAIN, true, 1);
+                if (phased && !c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);    // (MIW_BVH4=0: the phase machine steps through the BVH2, the MATS_TRIO class only)
+                else if (phased) {
+                    // the tree's width, and the Placed instantiations for a shard of about one pixel per resident lane (measuring, then placed launch)
+                    const miw_pick::Pick pick = miw_pick::tree_class(facts);
+                    const int wide = phased8 ? 2 : 1;
+#define MIW_PHASED_PICKED(M, A, WV, W, PL) if (pick.mats == (M) && pick.analytic == (A) && ph_waves == (WV) && wide == (W) && place == (PL)) MIW_PHASED_LAUNCH_(M, A, WV, W, PL); else
+                    MIW_PHASED_LIST(MIW_PHASED_PICKED) return fail(c, MI_ERR_STATE, "render: no k_path_phased<%d, %d, ., %d, %d, %d> in the library", pick.mats, (int) pick.analytic, ph_waves, wide, (int) place);
+#undef MIW_PHASED_PICKED
                 }
 #undef MIW_PHASED_LAUNCH
 #undef MIW_PHASED_LAUNCH_
-                else if (direct) {
-#define MIW_DIRECT_LAUNCH(T, M, A) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, INTEG_DIRECT>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
-                    if (tiny && c->lights_on) MIW_DIRECT_LAUNCH(1, MATS_LIGHTS, false);
-                    else if (tiny && c->nested) MIW_DIRECT_LAUNCH(1, MATS_NESTED, false);
-                    else if (c->lights_on) MIW_DIRECT_LAUNCH(0, MATS_LIGHTS, true);
-                    else if (c->nested) MIW_DIRECT_LAUNCH(0, MATS_NESTED, true);
-                    else if (tiny && c->textured) MIW_DIRECT_LAUNCH(1, MATS_ALL, false);
-                    else if (tiny) MIW_DIRECT_LAUNCH(1, MATS_PLAIN, false);
-                    else if (c->textured) MIW_DIRECT_LAUNCH(0, MATS_ALL, true);
-                    else MIW_DIRECT_LAUNCH(0, MATS_PLAIN, true);
-#undef MIW_DIRECT_LAUNCH
-                }
+                // the special instantiations of the packet kernel, in front of its table (none of them is ever the direct integrator's: `overlap` and `packet_shard4` above)
                 else if (Q.group_done && c->view.tri_count <= 32u)     // (overlap: tiny && diffuse_only) the instantiation that counts finished pixels per group of 64 tiles
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (Q.group_done)
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (packet_shard4 && !Q.group_done)
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
-                else if (tiny && c->diffuse_only && c->view.tri_count <= 32u) MIW_PATH_LAUNCH(2, MATS_DIFFUSE);   // 32-bit candidate masks (BASELINE config 2: 32 triangles)
-                else if (tiny && c->diffuse_only) MIW_PATH_LAUNCH(1, MATS_DIFFUSE);
-                else if (tiny && c->lights_on) MIW_PATH_LAUNCH(1, MATS_LIGHTS);
-                else if (tiny && c->nested) MIW_PATH_LAUNCH(1, MATS_NESTED);          // + wrapper resolution, null / thindielectric
-                else if (c->lights_on) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_LIGHTS, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
-                else if (c->nested) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_NESTED, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
-                else if (tiny && c->textured) MIW_PATH_LAUNCH(1, MATS_ALL);           // texture coordinates / bitmap lookups compiled in
-                else if (!tiny && c->textured) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_ALL, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
-                else if (tiny && c->view.tri_count <= 32u) MIW_PATH_LAUNCH(2, MATS_PLAIN);
-                else if (tiny) MIW_PATH_LAUNCH(1, MATS_PLAIN);
-                else if (c->rects.empty()) MIW_PATH_LAUNCH(0, MATS_PLAIN);
-                else MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 0, MATS_PLAIN, true>), pgrid, block, rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
-#undef MIW_PATH_LAUNCH
-            } else if (c->lights_on && direct && tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_LIGHTS, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->nested && direct && tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->lights_on && direct)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_LIGHTS, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->nested && direct)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->lights_on && tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_LIGHTS>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->nested && tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->lights_on)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_LIGHTS>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (c->nested)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_NESTED>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (direct && tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1, MATS_ALL, false, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (direct)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0, MATS_ALL, true, INTEG_DIRECT>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else if (tiny)
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 1>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
-            else
-                MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, 0>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr));
+                else {
+                    // kernel variants (kernel_pick.h): no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that variant fits 4 waves per
+                    // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
+                    const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, false);
+#define MIW_RESIDENT_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, I>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); else
+                    MIW_RESIDENT_LIST(MIW_RESIDENT_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<true, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
+#undef MIW_RESIDENT_LAUNCH
+                }
+            } else {
+                // the float64-atomics film: one workgroup per 16 x 16 pixels, three classes (kernel_pick.h: resident_atomic)
+                const miw_pick::Pick pick = miw_pick::resident_atomic(facts);
+#define MIW_ATOMIC_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, T, M, A, I>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr)); else
+                MIW_ATOMIC_LIST(MIW_ATOMIC_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<false, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
+#undef MIW_ATOMIC_LAUNCH
+            }
             if (Q.group_done) {                                      // the path kernel is in `s`: queue the replay beside it
                 const mi_status os = overlap_enqueue(c, ropt, P, s, T, replay, n_tiles, overlap_mode != 2);
                 if (os != MI_OK) return os;
@@ -2479,12 +2428,12 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
 
         // trees walked with the LDS stack: one persistent stream kernel serves the E and the S rays of an iteration
         // (device/stream_trace.h); MIW_STREAM=0 keeps the slice-per-workgroup kernels (A/B runs)
-        const bool stream_on = !(ropt.get("MIW_STREAM") && atoi(ropt.get("MIW_STREAM")) == 0);
+        const bool stream_on = !ropt.off("MIW_STREAM");
         const bool stream = stream_on && c->lds_cfg.stack && !c->lds_cfg.brute && c->lds_cfg.nodes_staged == 0;
         K.path_kernel = stream ? 2u : 0u;
         // round 6: the stream kernel walks the 8-wide tree (the phase machine's two walk bodies) wherever mi_bvh_build produced it; its hit records then
         // name triangles in that tree's order, so k_sort_hits and k_shade get the view with the triangles / vertex normals of that order
-        const bool stream8 = stream && c->view.nodes4 != nullptr && c->nodes8_count != 0u && !(ropt.get("MIW_BVH8") && atoi(ropt.get("MIW_BVH8")) == 0);
+        const bool stream8 = stream && tree8_on(c, ropt);
         SceneView pview = c->view;
         if (stream8) { pview.nodes8 = c->d_nodes8.p; pview.tris = c->d_tris8.p; if (pview.tri_vn) pview.tri_vn = c->d_tri_vn8.p; }
         K.tree_width = stream8 ? 8u : 0u;
