@@ -270,7 +270,10 @@ struct QueueWork {
 // Waves != 0 names the wavefronts per SIMD outright: <..., 4> of the plain-diffuse kernel is the 128-register form (no scratch) that a SHARD of at most four
 // wavefronts' worth of pixels per SIMD gets — a rank's eighth of a 1080p frame is 4 050 wavefronts for 1 024 SIMDs: a fifth wave slot would stay empty and the
 // 96-register squeeze costs each wavefront 3.4 % (r6n: 256.4 vs 248.0 ms with four workgroups per CU).
-template <bool UseLog, int Tiny, int Mats = MATS_ALL, bool Analytic = (Tiny == 0), uint32_t Integ = INTEG_PATH, bool Groups = false, int Waves = 0>
+// Feat (miw/scene.h: FEAT_*): the scene features compiled into the path integrator's pixel loop; FEAT_NONE is the LEAN twin of a packet kernel, for scenes with no
+// environment map, no vertex normals on shapes or emitter faces, rendered without the moment integrator (csrc/kernel_pick.h: packet_features; miwave.hip: MIW_LEAN_LIST).
+// Every other route of this kernel (direct integrator, float64-atomics film) ignores it.
+template <bool UseLog, int Tiny, int Mats = MATS_ALL, bool Analytic = (Tiny == 0), uint32_t Integ = INTEG_PATH, bool Groups = false, int Waves = 0, uint32_t Feat = FEAT_ALL>
 __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? MIW_DIRECT_WAVES : Tiny ? ((Mats == MATS_DIFFUSE && !MIW_SPECTRAL) ? (Tiny == 2 ? MIW_PACKET_WAVES : 4) : MIW_PACKET_WAVES_ALL) : MIW_TREE_WAVES) void k_path_resident(RenderParams P, SceneView sc, LaneQueues Q, double *accum, Counters *cnt,
                                                                TraceLds cfg, uint32_t sample_end, TileArgs T, uint32_t *next_pixel) {
     extern __shared__ uint4 smem[];
@@ -313,7 +316,7 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
         __shared__ uint32_t s_prog[MIW_BLOCK / 64];
         if (cfg.tail_prio) work.enable_tail_prio(sample_end, &s_prog[threadIdx.x >> 6]);
         if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<Mats, Analytic>(P, sc, sample_end, work, tr2, &local);
-        else pixel_stream_render<Mats, Analytic, Frames>(P, sc, sample_end, work, tr2, &local);
+        else pixel_stream_render<Mats, Analytic, Frames, Feat>(P, sc, sample_end, work, tr2, &local);
     } else if (lane < P.n_lanes) {
         U4 st = Q.st[lane];
         if (!(st.z & LF_DONE)) {

@@ -62,4 +62,22 @@ inline Pick tree_class(const Facts &f) {
     return { 0, PLAIN, !f.no_rects };
 }
 
+// ---- scene features of the packet path kernels --------------------------------------------------------------------------------------
+// Beside the class, k_path_resident<true, tiny != 0, ..., INTEG_PATH> takes a mask of the scene features compiled INTO it (miw/scene.h's FEAT_*
+// are these values, by name): routes whose test is false for every record of a scene that lacks the feature.
+enum : unsigned { FEAT_ENV = 1u, FEAT_SHAPE_NORMALS = 2u, FEAT_EMITTER_NORMALS = 4u, FEAT_MOMENT = 8u, FEAT_ALL = 15u, FEAT_NONE = 0u };
+
+// the features a render needs: the scene has an environment map / a shape with vertex normals / an area emitter whose mesh has them
+// (mi_scene_upload), and the moment integrator wraps this render (mi_render_cfg::moment_pass)
+inline unsigned packet_features(bool has_env, bool shape_normals, bool emitter_normals, bool moment) {
+    return (has_env ? FEAT_ENV : 0u) | (shape_normals ? FEAT_SHAPE_NORMALS : 0u) | (emitter_normals ? FEAT_EMITTER_NORMALS : 0u) | (moment ? FEAT_MOMENT : 0u);
+}
+// the masks that EXIST as instantiations: all and none, not sixteen
+inline bool packet_features_exist(unsigned mask) { return mask == FEAT_ALL || mask == FEAT_NONE; }
+// the mask a render gets. Unlike a class outside its list (an error), a mask outside falls back to FEAT_ALL: the full kernel is correct
+// for every scene, the lean one (FEAT_NONE) only for a scene with none of the four. `lean_on`: the MIW_LEAN switch.
+inline unsigned packet_features_kernel(unsigned needed, bool lean_on) { return lean_on && packet_features_exist(needed) ? needed : (unsigned) FEAT_ALL; }
+// the picks of resident_path() that have a lean twin (miwave.hip: MIW_LEAN_LIST): the packet kernels of the plain-diffuse and the MATS_PLAIN class
+inline bool packet_lean_class(const Pick &p) { return p.tiny != 0 && !p.analytic && (p.mats == DIFFUSE || p.mats == PLAIN); }
+
 }  // namespace miw_pick

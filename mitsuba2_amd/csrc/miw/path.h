@@ -162,7 +162,8 @@ MIW_HD void lane_begin_sample(const RenderParams &P, uint32_t pixel, LaneRegs &L
 
 // integrator.cpp:264-287 — convert, splat, advance
 // `sink(pixel, sample_idx, position_sample, aovs)` stands for block->put(position_sample, aovs), :285
-template <typename Sink>
+// Feat without FEAT_MOMENT (scene.h): the caller knows P.moment_pass to be 0
+template <uint32_t Feat = FEAT_ALL, typename Sink>
 MIW_HD void lane_finish_sample(const RenderParams &P, uint32_t pixel, LaneRegs &L, Sink sink) {
 #if MIW_SPECTRAL
     V3 xyz = spectrum_to_xyz(L.ray_weight * L.res, L.wl);   // :266-271
@@ -170,7 +171,7 @@ MIW_HD void lane_finish_sample(const RenderParams &P, uint32_t pixel, LaneRegs &
     V3 xyz = srgb_to_xyz(L.res);                         // :272-273 (ray_weight == 1 in RGB)
 #endif
     float aovs[5] = { xyz.x, xyz.y, xyz.z, (L.flags & LF_VALID_RAY) ? 1.f : 0.f, 1.f };
-    if (P.moment_pass) {                                 // moment.cpp:83-88: nested.XYZ and their squares ride along
+    if ((Feat & FEAT_MOMENT) && P.moment_pass) {         // moment.cpp:83-88: nested.XYZ and their squares ride along
         const float sq[3] = { sqr(xyz.x), sqr(xyz.y), sqr(xyz.z) };
         bool ok = true;                                  // ImageBlock::put tests all channels of the sample together; the block of an
         for (int k = 0; k < 3; ++k) ok = ok && isfinite_(aovs[k]) && isfinite_(sq[k]);   // integrator with AOVs has warn_negative = false (integrator.cpp:113)
@@ -331,7 +332,8 @@ MIW_HD constexpr bool mats_lights(int mats) { return mats == MATS_LIGHTS; }
 // `Analytic` = false compiles the analytic-shape branch out (scenes the caller knows to be triangles only).
 // `Frames` = true: the caller built SceneView::tri_frames / emit_face_n (the packet kernels; scene.h) — the per-triangle constants of
 // the interaction and of the emitter sample are read from them instead of being recomputed per segment.
-template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, typename PrevO, typename Cnt>
+// `Feat` (scene.h: FEAT_*): the scene features compiled in — the caller clears the bit of one its scene does not have.
+template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, uint32_t Feat = FEAT_ALL, typename PrevO, typename Cnt>
 MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4 h, PrevO prev_o,
                      ShadowOut &sh, Cnt *cnt_local) {
     sh.has = false;
@@ -344,8 +346,8 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     uint32_t bsdf_index = 0;
     int32_t emitter = -1;                            // scene.h:243-253 (no environment emitter)
     // only MATS_ALL kernels are launched for scenes with texture coordinates (miwave.hip: diffuse_only / textured)
-    if (valid) hit_surface_interaction<Analytic, mats_full(Mats), Frames>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
-    else emitter = miss_emitter<mats_lights(Mats)>(sc);   // a miss sees the environment, scene.h:248-249
+    if (valid) hit_surface_interaction<Analytic, mats_full(Mats), Frames, Feat>(sc, tri_idx, h.x, h.y, h.z, prev_o, ray_d, si, bsdf_index, emitter);
+    else emitter = miss_emitter<mats_lights(Mats), Feat>(sc);   // a miss sees the environment, scene.h:248-249
     if (depth == 1 && valid) L.flags |= LF_VALID_RAY;   // path.cpp:121
     MIW_SECTION(7);                                   // (sections 6.. : the shade body of the phase machine, debug builds)
 
@@ -364,11 +366,11 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
                     d = d / dist;
                     n = si.sh.n;
                 }
-                emitter_pdf = pdf_emitter_direction<Analytic, mats_lights(Mats)>(sc, (uint32_t) emitter, d, dist, n, ref_p);
+                emitter_pdf = pdf_emitter_direction<Analytic, mats_lights(Mats), Feat>(sc, (uint32_t) emitter, d, dist, n, ref_p);
             }
             emission_weight = mis_weight(L.prev_pdf, emitter_pdf);
         }
-        Spec radiance = valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : miss_eval<mats_lights(Mats)>(sc, ray_d, L.wl);
+        Spec radiance = valid ? emitter_eval(sc.emitters[emitter], si.wi, L.wl) : miss_eval<mats_lights(Mats), Feat>(sc, ray_d, L.wl);
         L.res = L.res + emission_weight * L.tp * radiance;
     }
 
@@ -402,7 +404,7 @@ MIW_HD int path_step(const RenderParams &P, const SceneView &sc, LaneRegs &L, F4
     // ---- emitter sampling, :155-172 ----
     if (bflags & BSDF_Smooth) {
         DirectionSample ds;
-        Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats), Frames>(sc, si.p, next_2d(L.rng), ds, L.wl);
+        Spec emitter_val = sample_emitter_direction<Analytic, mats_lights(Mats), Frames, Feat>(sc, si.p, next_2d(L.rng), ds, L.wl);
         if (ds.pdf != 0.f) {
             V3 wo = to_local(si.sh, ds.d);
             Spec bsdf_val = Mats == MATS_DIFFUSE ? diffuse_eval(*bsdf.b, si.wi, wo, tc) : bsdf_side_eval<Ext, Trio, Nested>(bsdf, si.wi, wo, tc);
@@ -512,7 +514,7 @@ MIW_HD uint32_t lane_shade(const RenderParams &P, const SceneView &sc, const Lan
 // store(st) publishes a pixel's state when its run is over, put(...) is block->put(). A lane that
 // finishes a pixel fetches the next one INSIDE the iteration loop, so the other lanes of its wavefront
 // never wait for it (the device feeds lanes from one shared queue; the CPU checker hands out one pixel).
-template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, typename Work, typename Trace2, typename Cnt>
+template <int Mats = MATS_ALL, bool Analytic = true, bool Frames = false, uint32_t Feat = FEAT_ALL, typename Work, typename Trace2, typename Cnt>
 MIW_HD void pixel_stream_render(const RenderParams &P, const SceneView &sc, uint32_t sample_end, Work &work,
                                 Trace2 trace2, Cnt *cnt_local) {
     LaneRegs L;
@@ -546,13 +548,13 @@ MIW_HD void pixel_stream_render(const RenderParams &P, const SceneView &sc, uint
         sh.has = false;
         int r = STEP_FINISHED;
         if (!dead_pending) {
-            r = path_step<Mats, Analytic, Frames>(P, sc, L, h, [o]() { return o; }, sh, cnt_local);
+            r = path_step<Mats, Analytic, Frames, Feat>(P, sc, L, h, [o]() { return o; }, sh, cnt_local);
             MIW_SECTION(4);
             if (r == STEP_DEAD_PENDING) { dead_pending = true; continue; }   // one more pass for its shadow ray
             if (r == STEP_CONTINUE) continue;
         }
         dead_pending = false;
-        lane_finish_sample(P, pixel, L, sink);
+        lane_finish_sample<Feat>(P, pixel, L, sink);
         if (cnt_local) cnt_local->samples++;
         L.flags = 0;
         lane_begin_sample(P, pixel, L, work.job_end(L.sample_idx, sample_end));   // (the end of this lane's JOB: the launch's last sample, or the chunk's)

@@ -9,6 +9,7 @@
 #include "bsdf.h"
 #include "envmap.h"
 #include "light.h"
+#include "../kernel_pick.h"
 
 namespace miw {
 
@@ -47,6 +48,14 @@ struct EmitterRec {
 };
 // (EmitterRec::type: the EMITTER_* values are defined in light.h)
 enum : uint32_t { SHAPE_HAS_NORMALS = 1u, SHAPE_HAS_TEXCOORDS = 8u };     // ShapeRec::flags (= MI_SHAPE_* of include/miwave.h)
+// Scene features a kernel may compile OUT (template parameter `Feat` of the functions below and of miw/path.h, a mask of the features compiled
+// IN; the default is all of them): routes that are a fact of the uploaded scene, not of a lane — a scene without an environment map, without
+// vertex normals on its shapes / on its emitter faces, a render without the moment integrator. A cleared bit promises that the route's test is
+// false for every record of the scene, so the values of the code that does run are what they were. Who clears one: csrc/kernel_pick.h
+// (packet_features), for the packet path kernels only.
+// The bits are defined once, beside the rule that picks a mask (csrc/kernel_pick.h, plain C++).
+enum : uint32_t { FEAT_ENV = miw_pick::FEAT_ENV, FEAT_SHAPE_NORMALS = miw_pick::FEAT_SHAPE_NORMALS, FEAT_EMITTER_NORMALS = miw_pick::FEAT_EMITTER_NORMALS,
+                  FEAT_MOMENT = miw_pick::FEAT_MOMENT, FEAT_ALL = miw_pick::FEAT_ALL, FEAT_NONE = miw_pick::FEAT_NONE };
 
 struct SceneView {
     const BvhNode *nodes;   uint32_t node_count;
@@ -92,7 +101,7 @@ MIW_HD PrimCtx prim_ctx(const SceneView &sc) { PrimCtx c; c.rects = sc.rects; c.
 // path out (scenes the caller knows to have none). One definition for the path kernels and for mi_ray_intersect.
 // Frames = true (the packet kernels, which built SceneView::tri_frames): the per-triangle half of compute_surface_interaction
 // comes from that table (shape.h: TriFrame).
-template <bool Analytic, bool Texcoords, bool Frames = false, typename RayO>
+template <bool Analytic, bool Texcoords, bool Frames = false, uint32_t Feat = FEAT_ALL, typename RayO>
 MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float t, float u, float v, RayO ray_o, V3 ray_d,
                                     SurfaceInteraction &si, uint32_t &bsdf_index, int32_t &emitter) {
     const Tri &tr = sc.tris[tri_idx];
@@ -102,7 +111,7 @@ MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float
         if (a.kind == ANALYTIC_SPHERE) compute_surface_interaction_sphere(a, t, ray_o(), ray_d, si);
         else compute_surface_interaction_rect(a, t, u, v, ray_o(), ray_d, si);
     } else {
-        const float *vn = (shape.flags & 1u) ? sc.tri_vn + 9 * (size_t) tri_idx : nullptr;
+        const float *vn = ((Feat & FEAT_SHAPE_NORMALS) && (shape.flags & 1u)) ? sc.tri_vn + 9 * (size_t) tri_idx : nullptr;
         const float *tc = (Texcoords && (shape.flags & SHAPE_HAS_TEXCOORDS)) ? sc.tri_uv + 6 * (size_t) tr.prim : nullptr;
         if constexpr (Frames) compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, sc.tri_frames[tri_idx], t, u, v, ray_d, si);
         else compute_surface_interaction(ld3(tr.p0), ld3(tr.p1), ld3(tr.p2), vn, tc, t, u, v, ray_d, si);
@@ -114,17 +123,18 @@ MIW_HD void hit_surface_interaction(const SceneView &sc, uint32_t tri_idx, float
 struct DirectionSample { V3 p, n, d; float dist, pdf; uint32_t emitter; bool delta; };   // delta: written and read by Lights = true code only
 
 // si.emitter(scene) of a ray that hit nothing (scene.h:248-249): the environment emitter — the environment map or, with Lights, the constant one
-template <bool Lights = false>
+template <bool Lights = false, uint32_t Feat = FEAT_ALL>
 MIW_HD int32_t miss_emitter(const SceneView &sc) {
-    if (sc.env) return (int32_t) sc.env->emitter_index;
+    if ((Feat & FEAT_ENV) && sc.env) return (int32_t) sc.env->emitter_index;
     if (Lights && sc.constant) return (int32_t) sc.constant->emitter_index;
     return -1;
 }
 
+template <uint32_t Feat = FEAT_ALL>
 MIW_HD MeshSampler emitter_mesh(const SceneView &sc, const EmitterRec &e) {
     MeshSampler m;
     m.tri = sc.emit_tri + 9 * (size_t) e.tri_first;
-    m.vnorm = (e.flags & 1u) ? sc.emit_vnorm + 9 * (size_t) e.tri_first : nullptr;
+    m.vnorm = ((Feat & FEAT_EMITTER_NORMALS) && (e.flags & 1u)) ? sc.emit_vnorm + 9 * (size_t) e.tri_first : nullptr;
     m.pmf = sc.emit_pmf + e.tri_first;
     m.cdf = sc.emit_cdf + e.tri_first;
     m.count = e.tri_count;
@@ -250,7 +260,8 @@ MIW_HD Spec env_eval_spec(const EnvmapRec &e, V3 d, const Wavelengths &) { retur
 // Analytic = false: the caller knows the scene to hold no analytic shapes, hence no sphere / rectangle lights (their code is compiled out).
 // Lights = true: the table may hold point / spot / directional / constant records (light.h); false compiles them out.
 // Frames = true: the normal of a sampled mesh face comes from SceneView::emit_face_n (the packet kernels).
-template <bool Analytic = true, bool Lights = false, bool Frames = false>
+// Feat: the environment-map arm and the vertex normals of emitter faces compiled in (FEAT_ENV, FEAT_EMITTER_NORMALS).
+template <bool Analytic = true, bool Lights = false, bool Frames = false, uint32_t Feat = FEAT_ALL>
 MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     const EmitterRec &e = sc.emitters[index];
     Spec value;
@@ -260,7 +271,7 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
         LightSample ls;
         value = light_sample_direction(sc.lights[e.tri_first], ref_p, sample, ls, wl);
         ds.p = ls.p; ds.n = ls.n; ds.d = ls.d; ds.dist = ls.dist; ds.pdf = ls.pdf; ds.delta = ls.delta;
-    } else if (e.type == EMITTER_ENVMAP) {
+    } else if ((Feat & FEAT_ENV) && e.type == EMITTER_ENVMAP) {
         value = env_sample_direction_spec(*sc.env, ref_p, sample, ds.d, ds.dist, ds.pdf, ds.p, ds.n, wl, env_top(sc));
     } else {
         if (Analytic && (e.flags & 2u) && sc.rects[e.tri_first].kind == ANALYTIC_SPHERE) {
@@ -269,8 +280,8 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
             // Shape::sample_direction, shape.cpp:292-309
             PositionSample ps;
             if (Analytic && (e.flags & 2u)) ps = rect_sample_position(sc.rects[e.tri_first], sample);
-            else if constexpr (Frames) ps = mesh_sample_position(emitter_mesh(sc, e), sample, FaceNormalTable{ sc.emit_face_n + 4 * (size_t) e.tri_first });
-            else ps = mesh_sample_position(emitter_mesh(sc, e), sample);
+            else if constexpr (Frames) ps = mesh_sample_position(emitter_mesh<Feat>(sc, e), sample, FaceNormalTable{ sc.emit_face_n + 4 * (size_t) e.tri_first });
+            else ps = mesh_sample_position(emitter_mesh<Feat>(sc, e), sample);
             ds.p = ps.p; ds.n = ps.n; ds.pdf = ps.pdf;
             ds.d = ds.p - ref_p;
             float dist_squared = squared_norm(ds.d);
@@ -290,7 +301,7 @@ MIW_HD Spec emitter_sample_direction(const SceneView &sc, uint32_t index, V3 ref
 // scene.cpp:164-200, *without* the visibility test (the shadow ray is a separate stage of the kernels;
 // mi_sample_emitter_direction traces it on request). Returns the unoccluded emitter value; `ds.pdf == 0`
 // means "no sample" (path.cpp:160).
-template <bool Analytic = true, bool Lights = false, bool Frames = false>
+template <bool Analytic = true, bool Lights = false, bool Frames = false, uint32_t Feat = FEAT_ALL>
 MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, DirectionSample &ds, const Wavelengths &wl) {
     if (sc.emitter_count == 0) {                       // scene.cpp:208-211
         ds.p = ds.n = ds.d = v3(0.f); ds.dist = 0.f; ds.pdf = 0.f; ds.emitter = 0;
@@ -306,7 +317,7 @@ MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, D
         index = i < sc.emitter_count - 1 ? i : sc.emitter_count - 1;
         sample.x = (sample.x - (float) index * emitter_pdf) * n;
     }
-    Spec value = emitter_sample_direction<Analytic, Lights, Frames>(sc, index, ref_p, sample, ds, wl);
+    Spec value = emitter_sample_direction<Analytic, Lights, Frames, Feat>(sc, index, ref_p, sample, ds, wl);
     if (sc.emitter_count > 1) {                        // scene.cpp:195-197
         ds.pdf *= emitter_pdf;
         value = value * rcp(emitter_pdf);
@@ -317,11 +328,11 @@ MIW_HD Spec sample_emitter_direction(const SceneView &sc, V3 ref_p, V2 sample, D
 // Endpoint::pdf_direction of emitter `emitter` (area.cpp:168-187 + shape.cpp:311-323, envmap.cpp:192-208).
 // `ds_d`, `ds_dist`, `ds_n` come from DirectionSample(si_bsdf, si) (records.h:167-173).
 // `ref_p` = it.p, the point the direction leaves from (only the sphere's pdf_direction needs it).
-template <bool Analytic = true, bool Lights = false>
+template <bool Analytic = true, bool Lights = false, uint32_t Feat = FEAT_ALL>
 MIW_HD float emitter_pdf_direction(const SceneView &sc, uint32_t emitter, V3 ds_d, float ds_dist, V3 ds_n, V3 ref_p) {
     const EmitterRec &e = sc.emitters[emitter];
     if (Lights && e.type >= EMITTER_POINT) return light_pdf_direction(sc.lights[e.tri_first]);
-    if (e.type == EMITTER_ENVMAP) return env_pdf_direction(*sc.env, ds_d);
+    if ((Feat & FEAT_ENV) && e.type == EMITTER_ENVMAP) return env_pdf_direction(*sc.env, ds_d);
     float dp = dot(ds_d, ds_n);
     bool active = dp < 0.f;
     float pdf;
@@ -335,9 +346,9 @@ MIW_HD float emitter_pdf_direction(const SceneView &sc, uint32_t emitter, V3 ds_
     return active ? pdf : 0.f;
 }
 // scene.cpp:216-231
-template <bool Analytic = true, bool Lights = false>
+template <bool Analytic = true, bool Lights = false, uint32_t Feat = FEAT_ALL>
 MIW_HD float pdf_emitter_direction(const SceneView &sc, uint32_t emitter, V3 ds_d, float ds_dist, V3 ds_n, V3 ref_p) {
-    float value = emitter_pdf_direction<Analytic, Lights>(sc, emitter, ds_d, ds_dist, ds_n, ref_p);
+    float value = emitter_pdf_direction<Analytic, Lights, Feat>(sc, emitter, ds_d, ds_dist, ds_n, ref_p);
     if (sc.emitter_count > 1) value = value * sc.emitter_count_inv;
     return value;
 }
@@ -347,9 +358,12 @@ MIW_HD Spec emitter_eval(const EmitterRec &e, V3 wi, const Wavelengths &wl) {
     return wi.z > 0.f ? tex_eval(e.radiance, wl) : spec(0.f);
 }
 // Endpoint::eval of the environment emitter a miss sees (miss_emitter() >= 0): envmap.cpp:134-147 or, with Lights, constant.cpp:61-65
-template <bool Lights = false>
+// Without FEAT_ENV and without Lights no miss sees an emitter (miss_emitter() is -1) and no lane gets here. The lookup is NOT compiled out for that
+// case all the same: with its body gone (and path_step told that an emitter hit is a hit) the headline's lean kernel is 300 vector instructions
+// shorter and keeps 20 values in scratch instead of 17 — the full kernel keeps 18 — for the same time, measured (profiles/r09_lean_packet.txt).
+template <bool Lights = false, uint32_t Feat = FEAT_ALL>
 MIW_HD Spec miss_eval(const SceneView &sc, V3 ray_d, const Wavelengths &wl) {
-    if (Lights && !sc.env) return light_eval(*sc.constant, wl);
+    if (Lights && (!(Feat & FEAT_ENV) || !sc.env)) return light_eval(*sc.constant, wl);
     return env_eval_spec(*sc.env, ray_d, wl);
 }
 

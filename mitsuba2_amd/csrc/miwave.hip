@@ -180,6 +180,7 @@ static const KnobInfo g_knobs[] = {
     { "MIW_PLACE", "0: shards of about one pixel per lane skip the measuring launch + placed queues" },
     { "MIW_JOB_CHUNK", "smallest chunk of a full frame's pixel jobs, in samples (a power of two; default 64, the phase machine 32): the pixels' sample streams are cut into halving chunks drawn chunk-major from one queue; 0: a job = all the samples of a pixel" },
     { "MIW_JOB_CHUNK_FORCE", "1: chunk jobs whatever the frame's size (tests of the hand-over between lanes)" },
+    { "MIW_LEAN", "0: a packet scene without environment map and vertex normals, rendered without the moment integrator, keeps the full path kernel instead of its lean twin (kernel_pick.h: packet_features)" },
     { "MIW_PACKET_SHARD4", "0: a plain-diffuse packet job of at most four wavefronts of pixels per SIMD keeps the five-wavefront (96-register) kernel" },
     { "MIW_PLACE_MEASURE", "divisor: the measuring launch runs spp / divisor samples" },
     { "MIW_PLACE_SPREAD", "0 | 1: placed pieces = consecutive sorted lanes | one lane of every cost stratum" },
@@ -243,6 +244,7 @@ struct mi_ctx {
     DevBuf<Bvh8Node> d_nodes8; DevBuf<Tri> d_tris8; DevBuf<float> d_tri_vn8; uint32_t nodes8_count = 0, nodes8_depth = 0;   // the 8-wide tree (miw/bvh8.h) and the triangles / vertex normals in its order
     DevBuf<float> d_env_data, d_env_levels; DevBuf<EnvmapRec> d_env; EnvmapRec env_host{}; size_t env_levels_total = 0;   // (host copy of the record: level offsets for the LDS staging)
     bool have_env = false;
+    bool shape_normals = false, emitter_normals = false;     // a shape / an area emitter's mesh has vertex normals; with have_env, the facts kernel_pick.h's packet_features reads
     SceneView view{};
     TraceLds lds_cfg{}; size_t lds_bytes = 0;
 
@@ -679,6 +681,7 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
         c->emitters.push_back(r);
     }
     if (!any_emit_normals) c->emit_vnorm.clear();
+    c->shape_normals = any_normals; c->emitter_normals = any_emit_normals;
     if (s->light_count) push_specials();
     else if (s->envmap && s->envmap->emitter_index >= s->emitter_count) push_env();
     if (c->lights_on) { c->nested = c->textured = true; c->diffuse_only = c->trio = false; }    // -> the MATS_LIGHTS kernels (the MATS_NESTED table + miw/light.h)
@@ -1320,6 +1323,10 @@ static_assert(miw_pick::ALL == MATS_ALL && miw_pick::DIFFUSE == MATS_DIFFUSE && 
 #define MIW_PHASED_LIST(X) MIW_TREE_CLASSES(X, 4, 2, true) MIW_TREE_CLASSES(X, 4, 2, false) MIW_TREE_CLASSES(X, 4, 1, true) MIW_TREE_CLASSES(X, 4, 1, false) MIW_TREE_CLASSES(X, 3, 1, false)
 // X(Mats, Analytic, NW, PP): k_path_pooled (the 8 x 2 shape is instantiated for the MATS_TRIO class only — BASELINE configs 3 / 4)
 #define MIW_POOLED_LIST(X) X(MATS_ALL, true, 12, 1) X(MATS_TRIO, false, 12, 1) X(MATS_TRIO, false, 8, 2) X(MATS_PLAIN, false, 12, 1) X(MATS_PLAIN, true, 12, 1)
+// X(Tiny, Mats): the packet path kernels with the sample log that have a LEAN twin, k_path_resident<true, Tiny, Mats, false, INTEG_PATH, false, 0, FEAT_NONE> (miw/scene.h: FEAT_*;
+// kernel_pick.h: packet_features, packet_lean_class) — and the four-wavefront shard form of the first, named where it is launched. Two masks per kernel, all and none:
+// a scene with any of the four features runs the full kernel, which is correct for every scene.
+#define MIW_LEAN_LIST(X) X(2, MATS_DIFFUSE) X(1, MATS_DIFFUSE) X(2, MATS_PLAIN) X(1, MATS_PLAIN)
 #define MIW_PICKED(T, M, A) (pick.tiny == (T) && pick.mats == (M) && pick.analytic == (A))
 
 // the scene facts the rules read, from the context and the options of this call
@@ -2132,6 +2139,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         // 128-register instantiation for four: resident_kernel.h; MIW_PACKET_SHARD4=0 keeps five)
         bool packet_shard4 = !phased && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct && c->view.tri_count <= 32u && MIW_PACKET_WAVES > 4 && film_mode == 1 && n_lanes <= 64u * 4u * n_simd;
         if (ropt.off("MIW_PACKET_SHARD4")) packet_shard4 = false;
+        // the scene features compiled into the packet path kernel (miw/scene.h: FEAT_*): facts of the uploaded scene and of this render; MIW_LEAN=0 keeps them all
+        const uint32_t feat = miw_pick::packet_features_kernel(miw_pick::packet_features(c->have_env, c->shape_normals, c->emitter_normals, cfg->moment_pass != 0), !ropt.off("MIW_LEAN"));
         const uint32_t res_waves_compiled = phased ? (uint32_t) ph_waves : !tiny ? (uint32_t) MIW_TREE_WAVES : (c->diffuse_only && !MIW_SPECTRAL ? (c->view.tri_count <= 32u && !packet_shard4 ? (uint32_t) MIW_PACKET_WAVES : 4u) : (uint32_t) MIW_PACKET_WAVES_ALL);
         // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
         // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
@@ -2181,6 +2190,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                              per_launch >= cfg->spp && cfg->timeout_s <= 0.f && n_tiles > 0;
         for (uint32_t done = 0; done < cfg->spp; ) {
             uint32_t end = cfg->spp - done < per_launch ? cfg->spp : done + per_launch;
+            uint32_t feat_launched = FEAT_ALL;                       // the mask of the instantiation this launch IS: set where a lean twin is launched (MIW_DEBUG prints it)
             if (film_mode == 1) {
                 // persistent grid: <= 4 workgroups per CU, fed from the shared pixel queue
                 HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, c->d_next_pixel.n * sizeof(uint32_t), s));
@@ -2344,12 +2354,20 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else if (Q.group_done)
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                else if (packet_shard4 && !Q.group_done && feat == FEAT_NONE) {
+                    feat_launched = FEAT_NONE;
+                    MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                }
                 else if (packet_shard4 && !Q.group_done)
                     MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
                 else {
                     // kernel variants (kernel_pick.h): no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that variant fits 4 waves per
                     // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
                     const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, false);
+                    // (the lean twins in front of the table: a mask that is no instantiation has become FEAT_ALL above, a class without a twin keeps the full kernel)
+#define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
+                    MIW_LEAN_LIST(MIW_LEAN_LAUNCH)
+#undef MIW_LEAN_LAUNCH
 #define MIW_RESIDENT_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, I>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); else
                     MIW_RESIDENT_LIST(MIW_RESIDENT_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<true, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_RESIDENT_LAUNCH
@@ -2367,6 +2385,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 if (c->replay_enqueued) { K.film_overlapped = 1u; K.film_groups = c->replay_launches; }
                 Q.group_done = nullptr; Q.group_expected = nullptr; Q.group_flag = nullptr;
             }
+            // which instantiation this launch was, said after the launch site set it: 0x0 only where a lean twin (FEAT_NONE) was launched — not for a class without
+            // a twin, the overlap's Groups = true pair, the direct integrator or the float64-atomics film, which run the full kernel whatever mask was chosen
+            if (ropt.get("MIW_DEBUG") && tiny && !phased) fprintf(stderr, "[miwave] packet path kernel launched: scene features 0x%x of 0x%x compiled in (mask chosen for the render: 0x%x)\n", feat_launched, (uint32_t) FEAT_ALL, feat);
             K.n_path++; K.iterations++;
             done = end;
             // cancel() / timeout take effect at launch granularity (the reference checks should_stop() per block)
