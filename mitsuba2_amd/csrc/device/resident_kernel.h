@@ -52,8 +52,12 @@ struct TileArgs {               // film_mode 2 in the resident plan; side == 0: 
 // instantiation of the plain-diffuse packet kernel, launched when that replay is asked for (the only path kernel a replay wavefront fits beside; the default
 // kernels stay as they were: the statements cost the packet kernel ~1 ms of its 247 even when switched off, the phase machine 16 more spilled registers).
 // Jobs: chunk jobs (below) compiled in — the packet kernels always, the phase machine's full-frame instantiations by MIW_PHASED_JOBS (phased_kernel.h).
-template <bool Placed = true, bool Clock = false, bool Groups = false, bool Jobs = true>
+// Frame: the launch-time facts of a full frame folded into the code (the FRAME twins of the lean packet kernels, k_path_resident<..., FEAT_FRAME>; csrc/kernel_pick.h:
+// frame_twin) — chunk jobs on (fetch is fetch_job, store the hand-over, exhausted() the parked-word test), one queue (Placed = false), 16-byte log records, no tail
+// priorities (tick is empty). Job sizes, log interleave and sample counts stay run-time values.
+template <bool Placed = true, bool Clock = false, bool Groups = false, bool Jobs = true, bool Frame = false>
 struct QueueWork {
+    static_assert(!Frame || (!Placed && !Groups && Jobs), "the frame twin: one queue of chunk jobs, no group counts");
     const LaneQueues *Q; uint32_t *next_pixel; uint32_t n_lanes, spp, lane, warn_negative;
     const FilmRec *film; const float *thr;      // 16-byte records (Q->log_rec): the film geometry and the phase thresholds in LDS
     // One queue over all lanes — or, for shards of at most one pixel per resident lane, PLACED queues (nq = one per SIMD of the
@@ -92,6 +96,7 @@ struct QueueWork {
     // slots, so throughput is what it was. Evaluated every 16th iteration (one wave-wide minimum of the lanes' sample counters).
     uint32_t ticks, quarter, tail_prio, sample_end_; uint32_t *prog;      // prog: this wavefront's word in LDS (the wave-wide minimum)
     __device__ __forceinline__ void tick(uint32_t sample_idx, bool has_pixel) {
+        if (Frame) return;
         if (!tail_prio) { ++ticks; return; }
         // (called from divergent code: the lanes that just fetched a pixel are not here — so no cross-lane shuffles; the
         // counter of the first active lane decides, the minimum goes through one LDS atomic per lane)
@@ -126,7 +131,7 @@ struct QueueWork {
     // 256: 230.6, jobs of whole pixels: 239.3) — so mi_render cuts chunks of at least 64 samples.
     typedef uint32_t U4v __attribute__((ext_vector_type(4)));
     __device__ __forceinline__ static uint32_t &job_pend() { __shared__ uint32_t s_job_pend[MIW_BLOCK]; return s_job_pend[threadIdx.x & (MIW_BLOCK - 1)]; }
-    __device__ __forceinline__ bool exhausted() const { return !Jobs || !Q->job_chunk || job_pend() == 0xffffffffu; }   // after fetch() said false: for good, or "ask again"
+    __device__ __forceinline__ bool exhausted() const { return (!Frame && (!Jobs || !Q->job_chunk)) || job_pend() == 0xffffffffu; }   // after fetch() said false: for good, or "ask again"
     __device__ __forceinline__ uint32_t job_end(uint32_t sample_idx, uint32_t sample_end) const {   // called after a sample has finished: sample_idx >= 1
         const uint32_t r = spp - sample_idx;                                                        // samples still to do: a chunk ends where that is a power of two >= job_min
         return Jobs && (r & (r - 1u)) == 0u && r >= Q->job_min ? sample_idx : sample_end;         // (job_min = 2^31 without chunks; r = 0 at the pixel's end: sample_end decides)
@@ -161,7 +166,7 @@ struct QueueWork {
         }
     }
     __device__ __forceinline__ bool fetch(uint32_t &pixel, U4 &st) {
-        if (Jobs && Q->job_chunk) return fetch_job(pixel, st);       // (wave-uniform)
+        if (Frame || (Jobs && Q->job_chunk)) return fetch_job(pixel, st);       // (wave-uniform)
         for (;;) {
             if (!Placed) {                                      // one queue: a ballot, one atomic, the lanes' ranks
                 const unsigned long long b = __ballot(1);
@@ -213,7 +218,7 @@ struct QueueWork {
         return Clock ? (uint32_t) (__builtin_amdgcn_s_memtime() >> 8) : ticks;      // units of 256 shader cycles, or wavefront iterations
     }
     __device__ __forceinline__ void store(U4 st) {
-        if (Jobs && Q->job_chunk) {                             // chunk jobs: another lane (another XCD) takes the pixel on inside this launch
+        if (Frame || (Jobs && Q->job_chunk)) {                  // chunk jobs: another lane (another XCD) takes the pixel on inside this launch
             unsigned long long *words = reinterpret_cast<unsigned long long *>(Q->st + lane);
             __hip_atomic_store(words, (unsigned long long) st.x | ((unsigned long long) st.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the RNG words have landed before the counter that publishes them leaves
@@ -234,7 +239,7 @@ struct QueueWork {
         }
     }
     __device__ __forceinline__ void put(uint32_t pixel, uint32_t sample_idx, V2 pos, const float *aovs) {
-        if (Q->log_rec) {                                       // wave-uniform: one format per render
+        if (Frame || Q->log_rec) {                              // wave-uniform: one format per render
             LogSink16<const float *> sink{ Q->log_rec, thr, film, lane, spp, Q->log_rej & 255u, Q->log_rej >> 8 };   // (log_rej: the class count | log_il << 8 — one uniform, the phase machine has no scalar register to spare)
             sink(pixel, sample_idx, pos, aovs);
         } else {
@@ -273,12 +278,17 @@ struct QueueWork {
 // Feat (miw/scene.h: FEAT_*): the scene features compiled into the path integrator's pixel loop; FEAT_NONE is the LEAN twin of a packet kernel, for scenes with no
 // environment map, no vertex normals on shapes or emitter faces, rendered without the moment integrator (csrc/kernel_pick.h: packet_features; miwave.hip: MIW_LEAN_LIST).
 // Every other route of this kernel (direct integrator, float64-atomics film) ignores it.
+// Feat = FEAT_FRAME is the FRAME twin of a lean packet kernel: no scene feature, and what the launch of a full frame fixes for its whole duration compiled in instead of tested
+// in the pixel loop — chunk jobs from one queue, the 16-byte log, no tail priorities (QueueWork<..., Frame>), the leaf filter on (trace2<..., Filtered>). csrc/kernel_pick.h:
+// frame_twin says which launch takes it. (A value of Feat, not a parameter of its own: every other instantiation keeps its name.)
 template <bool UseLog, int Tiny, int Mats = MATS_ALL, bool Analytic = (Tiny == 0), uint32_t Integ = INTEG_PATH, bool Groups = false, int Waves = 0, uint32_t Feat = FEAT_ALL>
 __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? MIW_DIRECT_WAVES : Tiny ? ((Mats == MATS_DIFFUSE && !MIW_SPECTRAL) ? (Tiny == 2 ? MIW_PACKET_WAVES : 4) : MIW_PACKET_WAVES_ALL) : MIW_TREE_WAVES) void k_path_resident(RenderParams P, SceneView sc, LaneQueues Q, double *accum, Counters *cnt,
                                                                TraceLds cfg, uint32_t sample_end, TileArgs T, uint32_t *next_pixel) {
+    constexpr bool Frame = (Feat & FEAT_FRAME) != 0;
+    static_assert(!Frame || (UseLog && Tiny != 0 && !Analytic && Integ == INTEG_PATH && !Groups && Waves == 0 && Feat == FEAT_FRAME), "a frame twin is the twin of a lean packet kernel");
     extern __shared__ uint4 smem[];
     stage_to_lds(sc, cfg, smem);
-    const float *thr = stage_thresholds(smem, cfg, UseLog && Q.log_rec ? Q.log_thr : nullptr);
+    const float *thr = stage_thresholds(smem, cfg, UseLog && (Frame || Q.log_rec) ? Q.log_thr : nullptr);
     // (stage_tables:) the path kernels among the packet kernels also BUILD SceneView::tri_frames / emit_face_n there and read them (scene.h: Frames) — a compile-time property of the
     // instantiation. Not the direct-integrator kernels: compiled for three wavefronts per SIMD they keep ~40 values in scratch, and with the tables the
     // MATS_NESTED / MATS_LIGHTS ones keep three more than tests/test_nested_kernel_budget.py / test_lights_kernel_budget.py allow (168 / 164 B per lane for 156 / 152)
@@ -308,15 +318,17 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
     auto tr2 = [&](V3 o, float mint, V3 dE, float maxtE, bool hasE, V3 dS, float maxtS, bool hasS, F4 &hE, bool &occS) {
         // (LeafPairs: the leaf pass on pre-widened operands, trace.h — not in the direct-integrator kernels: compiled for three wavefronts per SIMD they keep ~40 values in
         // scratch as it is, and with it the MATS_LIGHTS one keeps 184 B per lane where tests/test_lights_kernel_budget.py allows 152)
-        trace2<Tiny, Analytic, Integ != INTEG_DIRECT>(sc, cfg, smem, o, mint, dE, maxtE, hasE, dS, maxtS, hasS, hE, occS);
+        trace2<Tiny, Analytic, Integ != INTEG_DIRECT, Frame>(sc, cfg, smem, o, mint, dE, maxtE, hasE, dS, maxtS, hasS, hE, occS);
     };
     if (UseLog) {
-        QueueWork<Tiny != 0, false, Groups> work; work.Q = &Q; work.next_pixel = next_pixel; work.n_lanes = P.n_lanes; work.spp = P.spp; work.lane = 0; work.warn_negative = P.film.warn_negative;
+        QueueWork<Tiny != 0 && !Frame, false, Groups, true, Frame> work; work.Q = &Q; work.next_pixel = next_pixel; work.n_lanes = P.n_lanes; work.spp = P.spp; work.lane = 0; work.warn_negative = P.film.warn_negative;
         work.film = &P.film; work.thr = thr; work.init_queues(cfg.queues ? cfg.queues : 1u);
-        __shared__ uint32_t s_prog[MIW_BLOCK / 64];
-        if (cfg.tail_prio) work.enable_tail_prio(sample_end, &s_prog[threadIdx.x >> 6]);
+        if constexpr (!Frame) {
+            __shared__ uint32_t s_prog[MIW_BLOCK / 64];
+            if (cfg.tail_prio) work.enable_tail_prio(sample_end, &s_prog[threadIdx.x >> 6]);
+        }
         if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<Mats, Analytic>(P, sc, sample_end, work, tr2, &local);
-        else pixel_stream_render<Mats, Analytic, Frames, Feat>(P, sc, sample_end, work, tr2, &local);
+        else pixel_stream_render<Mats, Analytic, Frames, Feat & FEAT_ALL>(P, sc, sample_end, work, tr2, &local);
     } else if (lane < P.n_lanes) {
         U4 st = Q.st[lane];
         if (!(st.z & LF_DONE)) {

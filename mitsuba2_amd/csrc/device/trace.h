@@ -496,13 +496,14 @@ __device__ __forceinline__ bool trace_one(const SceneView &sc, TraceLds cfg, con
 // `Tiny` selects the code that is compiled in: the two-phase LDS query (tiny scenes) or the tree walks —
 // one kernel per scene class keeps each one's register budget (occupancy) to what it needs.
 // `LeafPairs`: the leaf pass runs on LeafRay operands (the widening hoisted out of its loop; rays with mint >= 0 — the render kernels).
-template <int Tiny, bool Analytic = true, bool LeafPairs = false>
+// `Filtered`: the caller knows the leaf filter to be on (cfg.leaves != 0: the frame twins, resident_kernel.h) — the sweep of the MI_BVH_NO_LEAF_FILTER route is not compiled in.
+template <int Tiny, bool Analytic = true, bool LeafPairs = false, bool Filtered = false>
 __device__ __forceinline__ void trace2(const SceneView &sc, TraceLds cfg, const uint4 *smem,
                                        V3 o, float mint, V3 dE, float maxtE, bool hasE,
                                        V3 dS, float maxtS, bool hasS, F4 &hit_out, bool &occ_out) {
     Hit h; h.t = MIW_INFINITY; h.u = h.v = 0.f; h.tri = MIW_MISS; h.prim = 0xffffffffu;
     bool occ = false;
-    if (Tiny && cfg.leaves) {
+    if (Tiny && (Filtered || cfg.leaves)) {
         // candidate masks: 32 bits when the scene has <= 32 triangles (Tiny == 2), else 64
         using Mask = typename std::conditional<Tiny == 2, uint32_t, unsigned long long>::type;
         auto lowest = [](Mask m) -> uint32_t {

@@ -66,6 +66,9 @@ inline Pick tree_class(const Facts &f) {
 // Beside the class, k_path_resident<true, tiny != 0, ..., INTEG_PATH> takes a mask of the scene features compiled INTO it (miw/scene.h's FEAT_*
 // are these values, by name): routes whose test is false for every record of a scene that lacks the feature.
 enum : unsigned { FEAT_ENV = 1u, FEAT_SHAPE_NORMALS = 2u, FEAT_EMITTER_NORMALS = 4u, FEAT_MOMENT = 8u, FEAT_ALL = 15u, FEAT_NONE = 0u };
+// One more value of that template argument, beyond the scene features and never combined with one: the FRAME twin of a lean kernel (no scene feature, and the facts of a
+// full frame's launch compiled in: frame_twin below). A value of the mask rather than a parameter of its own, so that the kernels that do not have it keep their names.
+enum : unsigned { FEAT_FRAME = 16u };
 
 // the features a render needs: the scene has an environment map / a shape with vertex normals / an area emitter whose mesh has them
 // (mi_scene_upload), and the moment integrator wraps this render (mi_render_cfg::moment_pass)
@@ -79,5 +82,23 @@ inline bool packet_features_exist(unsigned mask) { return mask == FEAT_ALL || ma
 inline unsigned packet_features_kernel(unsigned needed, bool lean_on) { return lean_on && packet_features_exist(needed) ? needed : (unsigned) FEAT_ALL; }
 // the picks of resident_path() that have a lean twin (miwave.hip: MIW_LEAN_LIST): the packet kernels of the plain-diffuse and the MATS_PLAIN class
 inline bool packet_lean_class(const Pick &p) { return p.tiny != 0 && !p.analytic && (p.mats == DIFFUSE || p.mats == PLAIN); }
+
+// ---- the frame twins of the lean packet kernels -------------------------------------------------------------------------------------
+// k_path_resident<true, tiny, class, false, INTEG_PATH, false, 0, FEAT_FRAME> (device/resident_kernel.h): a lean twin with the facts the
+// launch of a full frame fixes for its whole duration compiled in, instead of tested inside the pixel loop with the other side of each test behind it.
+struct LaunchFacts {
+    bool job_chunks;      // LaneQueues::job_chunk != 0: chunk jobs from the one queue
+    bool log_rec16;       // LaneQueues::log_rec: the 16-byte sample log (a filter with class tables)
+    bool one_queue;       // TraceLds::queues == 1: no placed queues
+    bool tail_prio;       // TraceLds::tail_prio: least-progress-first wave priorities
+    bool leaf_filter;     // TraceLds::leaves != 0: not uploaded with MI_BVH_NO_LEAF_FILTER
+    bool group_counts;    // LaneQueues::group_done: the film replay runs beside the render
+};
+// the launch that takes the twin: one that would launch the lean twin of `p` (the path integrator, the mask FEAT_NONE, a class of MIW_LEAN_LIST) with every
+// fact as the twin has it compiled in. `twin_on`: the MIW_FRAME_TWIN switch. Anything else launches what it launched before.
+inline bool frame_twin(const Pick &p, bool direct, unsigned feat, const LaunchFacts &l, bool twin_on) {
+    return twin_on && !direct && feat == FEAT_NONE && packet_lean_class(p) &&
+           l.job_chunks && l.log_rec16 && l.one_queue && !l.tail_prio && l.leaf_filter && !l.group_counts;
+}
 
 }  // namespace miw_pick

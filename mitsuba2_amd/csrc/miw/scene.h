@@ -55,7 +55,8 @@ enum : uint32_t { SHAPE_HAS_NORMALS = 1u, SHAPE_HAS_TEXCOORDS = 8u };     // Sha
 // (packet_features), for the packet path kernels only.
 // The bits are defined once, beside the rule that picks a mask (csrc/kernel_pick.h, plain C++).
 enum : uint32_t { FEAT_ENV = miw_pick::FEAT_ENV, FEAT_SHAPE_NORMALS = miw_pick::FEAT_SHAPE_NORMALS, FEAT_EMITTER_NORMALS = miw_pick::FEAT_EMITTER_NORMALS,
-                  FEAT_MOMENT = miw_pick::FEAT_MOMENT, FEAT_ALL = miw_pick::FEAT_ALL, FEAT_NONE = miw_pick::FEAT_NONE };
+                  FEAT_MOMENT = miw_pick::FEAT_MOMENT, FEAT_ALL = miw_pick::FEAT_ALL, FEAT_NONE = miw_pick::FEAT_NONE,
+                  FEAT_FRAME = miw_pick::FEAT_FRAME };     // (no scene feature: the frame twin of a lean packet kernel, device/resident_kernel.h)
 
 struct SceneView {
     const BvhNode *nodes;   uint32_t node_count;

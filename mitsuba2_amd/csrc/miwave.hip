@@ -175,12 +175,13 @@ static const KnobInfo g_knobs[] = {
     { "MIW_POOLED", "1: tree scenes take k_path_pooled (walk jobs pooled across the workgroup; experimental, slower: DESIGN.md)" },
     { "MIW_POOL_SHAPE", "12x1 | 8x2: wavefronts per workgroup x pixels per lane of k_path_pooled" },
     { "MIW_POOL_VOTE", "shade_min:walk_min:node_min:tri_min:claim_min of k_path_pooled" },
-    { "MIW_TAIL_PRIO", "0: no least-progress-first wave priorities" },
+    { "MIW_TAIL_PRIO", "0: no least-progress-first wave priorities; 1: also in a packet kernel's launch of chunk jobs, which runs without them by default (and then keeps its lean kernel instead of the frame twin)" },
     { "MIW_WG_PER_CU", "workgroups per CU of the packet kernels' persistent grid" },
     { "MIW_PLACE", "0: shards of about one pixel per lane skip the measuring launch + placed queues" },
     { "MIW_JOB_CHUNK", "smallest chunk of a full frame's pixel jobs, in samples (a power of two; default 64, the phase machine 32): the pixels' sample streams are cut into halving chunks drawn chunk-major from one queue; 0: a job = all the samples of a pixel" },
     { "MIW_JOB_CHUNK_FORCE", "1: chunk jobs whatever the frame's size (tests of the hand-over between lanes)" },
     { "MIW_LEAN", "0: a packet scene without environment map and vertex normals, rendered without the moment integrator, keeps the full path kernel instead of its lean twin (kernel_pick.h: packet_features)" },
+    { "MIW_FRAME_TWIN", "0: a full frame of chunk jobs keeps the lean twin of its packet path kernel instead of the frame twin, which has the facts of such a launch compiled in (kernel_pick.h: frame_twin)" },
     { "MIW_PACKET_SHARD4", "0: a plain-diffuse packet job of at most four wavefronts of pixels per SIMD keeps the five-wavefront (96-register) kernel" },
     { "MIW_PLACE_MEASURE", "divisor: the measuring launch runs spp / divisor samples" },
     { "MIW_PLACE_SPREAD", "0 | 1: placed pieces = consecutive sorted lanes | one lane of every cost stratum" },
@@ -1325,7 +1326,8 @@ static_assert(miw_pick::ALL == MATS_ALL && miw_pick::DIFFUSE == MATS_DIFFUSE && 
 #define MIW_POOLED_LIST(X) X(MATS_ALL, true, 12, 1) X(MATS_TRIO, false, 12, 1) X(MATS_TRIO, false, 8, 2) X(MATS_PLAIN, false, 12, 1) X(MATS_PLAIN, true, 12, 1)
 // X(Tiny, Mats): the packet path kernels with the sample log that have a LEAN twin, k_path_resident<true, Tiny, Mats, false, INTEG_PATH, false, 0, FEAT_NONE> (miw/scene.h: FEAT_*;
 // kernel_pick.h: packet_features, packet_lean_class) — and the four-wavefront shard form of the first, named where it is launched. Two masks per kernel, all and none:
-// a scene with any of the four features runs the full kernel, which is correct for every scene.
+// a scene with any of the four features runs the full kernel, which is correct for every scene. Each of the four also has a FRAME twin, k_path_resident<..., FEAT_FRAME>
+// (resident_kernel.h; kernel_pick.h: frame_twin): the lean twin with the facts of a full frame's launch compiled in.
 #define MIW_LEAN_LIST(X) X(2, MATS_DIFFUSE) X(1, MATS_DIFFUSE) X(2, MATS_PLAIN) X(1, MATS_PLAIN)
 #define MIW_PICKED(T, M, A) (pick.tiny == (T) && pick.mats == (M) && pick.analytic == (A))
 
@@ -2191,6 +2193,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         for (uint32_t done = 0; done < cfg->spp; ) {
             uint32_t end = cfg->spp - done < per_launch ? cfg->spp : done + per_launch;
             uint32_t feat_launched = FEAT_ALL;                       // the mask of the instantiation this launch IS: set where a lean twin is launched (MIW_DEBUG prints it)
+            bool frame_launched = false;                             // ... and whether it is a frame twin: set where one is launched
             if (film_mode == 1) {
                 // persistent grid: <= 4 workgroups per CU, fed from the shared pixel queue
                 HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, c->d_next_pixel.n * sizeof(uint32_t), s));
@@ -2296,9 +2299,11 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 // least-progress-first wave priorities (QueueWork::tick): the wavefronts of a SIMD finish together instead of the most
                 // expensive one running on alone. Made for shards of about one pixel per resident lane (1/8 of C2: path kernel 50.1 ->
                 // 42.3 ms; 1/8 of the material balls -14 %), it also shortens the drain of a full frame (C2 275.9 -> 268.7 ms), so it is
-                // always on. MIW_TAIL_PRIO = 0 | 1 overrides.
-                rcfg.tail_prio = 1u;
-                if (ropt.off("MIW_TAIL_PRIO")) rcfg.tail_prio = 0u;
+                // always on — but for a packet kernel's launch of chunk jobs, whose tail is one chunk long: with and without them it took the same time in every configuration
+                // (r6t: C2 path kernel 222.01 221.47 ms with / 221.17 220.93 without, C5 573.9 / 573.5, direct 79.7 / 79.8), and the frame twins compile them out
+                // (kernel_pick.h: frame_twin). MIW_TAIL_PRIO = 0 | 1 overrides.
+                rcfg.tail_prio = tiny && Q.job_chunk ? 0u : 1u;
+                if (const char *e = ropt.get("MIW_TAIL_PRIO")) rcfg.tail_prio = atoi(e) != 0 ? 1u : 0u;
                 TraceLds ph_cfg = rcfg;
                 ph_cfg.shade_num = 2; ph_cfg.shade_den = c->have_env ? 4 : 3;
                 if (const char *e = ropt.get("MIW_SHADE_VOTE")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0) { ph_cfg.shade_num = (uint32_t) a; ph_cfg.shade_den = (uint32_t) b; } }
@@ -2365,6 +2370,15 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
                     const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, false);
                     // (the lean twins in front of the table: a mask that is no instantiation has become FEAT_ALL above, a class without a twin keeps the full kernel)
+                    // (... and the frame twins in front of those: a lean twin's launch whose facts are the ones the twin has compiled in — chunk jobs from one queue, the 16-byte
+                    // log, no tail priorities, the leaf filter on, no group counts; MIW_FRAME_TWIN=0 keeps the lean twin)
+                    miw_pick::LaunchFacts lf;
+                    lf.job_chunks = Q.job_chunk != 0u; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = rcfg.queues == 1u; lf.tail_prio = rcfg.tail_prio != 0u;
+                    lf.leaf_filter = c->lds_cfg.leaves != 0u; lf.group_counts = Q.group_done != nullptr;
+                    const bool frame = miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
+#define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
+                    MIW_LEAN_LIST(MIW_FRAME_LAUNCH)
+#undef MIW_FRAME_LAUNCH
 #define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
                     MIW_LEAN_LIST(MIW_LEAN_LAUNCH)
 #undef MIW_LEAN_LAUNCH
@@ -2388,6 +2402,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
             // which instantiation this launch was, said after the launch site set it: 0x0 only where a lean twin (FEAT_NONE) was launched — not for a class without
             // a twin, the overlap's Groups = true pair, the direct integrator or the float64-atomics film, which run the full kernel whatever mask was chosen
             if (ropt.get("MIW_DEBUG") && tiny && !phased) fprintf(stderr, "[miwave] packet path kernel launched: scene features 0x%x of 0x%x compiled in (mask chosen for the render: 0x%x)\n", feat_launched, (uint32_t) FEAT_ALL, feat);
+            if (ropt.get("MIW_DEBUG") && tiny && !phased) fprintf(stderr, "[miwave] packet path kernel launched: frame twin %s\n", frame_launched ? "yes (chunk jobs, one queue, 16-byte log, no tail priorities, leaf filter compiled in)" : "no");
             K.n_path++; K.iterations++;
             done = end;
             // cancel() / timeout take effect at launch granularity (the reference checks should_stop() per block)
