@@ -732,29 +732,15 @@ __device__ __forceinline__ void film_lanes_pixel(miw_f2 (&acc)[MIW_FL_BS][MIW_FL
 #ifndef MIW_FL_WAVES
 #define MIW_FL_WAVES 3
 #endif
-// WV = wavefronts per SIMD the kernel is compiled for: 3 (168 registers; the replay on its own) or, with U = 2, 4 (128 registers, the sample loops still free
-// of scratch: tests/test_kernel_budget.py) — the form that fits BESIDE three wavefronts of the 120-register packet kernel (miwave.hip: overlap_enqueue).
-template <int U, int NT, int WV = MIW_FL_WAVES>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WV, 8))) void k_film_lanes(FilmRec F, BlockReplayArgs A, PatchArgs PA /* patches_x / _y = texel blocks per tile row / column */, uint32_t n_tiles, float *tiles,
-                  uint32_t group0 /* the first group of 64 tiles this launch replays (several launches when the replay runs beside the render: miwave.hip, overlap_enqueue) */,
-                  uint32_t prio /* s_setprio of its wavefronts, 0 .. 3 (beside the path kernel, whose wavefronts raise theirs: resident_kernel.h tick()) */) {
-    if (prio == 3u) __builtin_amdgcn_s_setprio(3); else if (prio == 2u) __builtin_amdgcn_s_setprio(2); else if (prio == 1u) __builtin_amdgcn_s_setprio(1);
+// One block position of 64 tiles, from its window list to the write-out of the lanes' 4 x 4 blocks: what a wavefront of k_film_lanes does once and one of
+// k_film_chains once per position of its chain. `s_w` holds the class weights (filled by the caller), `s_list` takes the window list.
+template <int U, int NT>
+__device__ __forceinline__ void film_lanes_block(const FilmRec F, const BlockReplayArgs A, float *tiles, const uint32_t tile, const bool live, const BlockGeom g,
+                                                 const int tx0, const int ty0, float *s_w, unsigned short *s_list) {
     constexpr int BS = MIW_FL_BS, WS = MIW_FQ_WSTRIDE(MIW_FL_BS), LEAD = BS - 1, LCAP = 64;
-    extern __shared__ float s_w[];                           // (count + 1) x WS weights; row `count` = 0
-    __shared__ unsigned short s_list[LCAP];
     const uint32_t l = threadIdx.x;
-    const uint32_t n_pos = PA.patches_x * PA.patches_y;
-    const uint32_t tw = blockIdx.x / n_pos + group0, pos = blockIdx.x % n_pos;
-    const int tx0 = (int) (pos % PA.patches_x) * BS, ty0 = (int) (pos / PA.patches_x) * BS;      // (wave-uniform) the block inside its tile
-    const uint32_t tile = tw * 64u + l;
-    const bool live = tile < n_tiles;
-    const BlockGeom g = block_geom(F, A.blocks_x, live ? (A.tile_list ? A.tile_list[tile] : tile) : 0u);
     const uint32_t rej = A.cls.count;                        // the zero row (LogSink16 logs rejected samples with class `count`)
     const int reach = A.cls.reach;                           // <= 2 (the host launches the other kernels otherwise)
-    for (uint32_t i = l; i < (rej + 1u) * WS; i += 64u) {
-        const uint32_t c = i / WS, a = i % WS;
-        s_w[i] = (c < rej && a >= (uint32_t) LEAD && a <= (uint32_t) LEAD + 2u * (uint32_t) reach) ? A.cls.w[c * MIW_FC_STRIDE + a - LEAD] : 0.f;
-    }
     // ---- the pixels within reach of the block, in Morton order: the same list in every tile ----
     const uint32_t bs2 = 1u << A.bs2_log2;
     uint32_t fill = 0;
@@ -843,6 +829,59 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WV, 8))) voi
 #pragma unroll
                 for (int k = 0; k < MIW_FILM_CHANNELS; ++k) out[k] = (c & 1) ? acc[r][c / 2][k].y : acc[r][c / 2][k].x;
             }
+}
+// the class weights in LDS: (count + 1) rows of WS floats, a window's 2 reach + 1 weights behind LEAD zeros; row `count` = 0
+__device__ __forceinline__ void film_lanes_weights(const BlockReplayArgs &A, float *s_w) {
+    constexpr int BS = MIW_FL_BS, WS = MIW_FQ_WSTRIDE(MIW_FL_BS), LEAD = BS - 1;
+    const uint32_t rej = A.cls.count;
+    const int reach = A.cls.reach;
+    for (uint32_t i = threadIdx.x; i < (rej + 1u) * WS; i += 64u) {
+        const uint32_t c = i / WS, a = i % WS;
+        s_w[i] = (c < rej && a >= (uint32_t) LEAD && a <= (uint32_t) LEAD + 2u * (uint32_t) reach) ? A.cls.w[c * MIW_FC_STRIDE + a - LEAD] : 0.f;
+    }
+}
+// WV = wavefronts per SIMD the kernel is compiled for: 3 (168 registers; the replay on its own) or, with U = 2, 4 (128 registers, the sample loops still free
+// of scratch: tests/test_kernel_budget.py) — the form that fits BESIDE three wavefronts of the 120-register packet kernel (miwave.hip: overlap_enqueue).
+template <int U, int NT, int WV = MIW_FL_WAVES>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WV, 8))) void k_film_lanes(FilmRec F, BlockReplayArgs A, PatchArgs PA /* patches_x / _y = texel blocks per tile row / column */, uint32_t n_tiles, float *tiles,
+                  uint32_t group0 /* the first group of 64 tiles this launch replays (several launches when the replay runs beside the render: miwave.hip, overlap_enqueue) */,
+                  uint32_t prio /* s_setprio of its wavefronts, 0 .. 3 (beside the path kernel, whose wavefronts raise theirs: resident_kernel.h tick()) */) {
+    if (prio == 3u) __builtin_amdgcn_s_setprio(3); else if (prio == 2u) __builtin_amdgcn_s_setprio(2); else if (prio == 1u) __builtin_amdgcn_s_setprio(1);
+    extern __shared__ float s_w[];                           // (count + 1) x WS weights; row `count` = 0
+    __shared__ unsigned short s_list[64];
+    const uint32_t n_pos = PA.patches_x * PA.patches_y;
+    const uint32_t tw = blockIdx.x / n_pos + group0, pos = blockIdx.x % n_pos;
+    const int tx0 = (int) (pos % PA.patches_x) * MIW_FL_BS, ty0 = (int) (pos / PA.patches_x) * MIW_FL_BS;
+    const uint32_t tile = tw * 64u + threadIdx.x;
+    const bool live = tile < n_tiles;
+    const BlockGeom g = block_geom(F, A.blocks_x, live ? (A.tile_list ? A.tile_list[tile] : tile) : 0u);
+    film_lanes_weights(A, s_w);
+    film_lanes_block<U, NT>(F, A, tiles, tile, live, g, tx0, ty0, s_w, s_list);
+}
+
+// Round 11: the same replay in EQUAL CHAINS. k_film_lanes' wavefronts are all resident at once and differ in length (a position in a tile's interior
+// replays 64 pixel runs of 32-pixel tiles, one at an edge 32, a corner 16), so the launch lasts as long as an interior wavefront while the others have
+// long ended and the demand on HBM has fallen. Here a wavefront = (a group of 64 tiles, a CHAIN of positions): csrc/film_chains.h packs the positions
+// into chains no heavier than one interior position (64 chains of 64 runs for 32-pixel tiles: 49 interior positions, 14 pairs of edges, the four
+// corners), `chains` = start[0 .. n_chains] then the positions chain by chain. A position's additions are film_lanes_block's, its texels its own:
+// the tiles are those of k_film_lanes bit for bit. The workgroup is one wavefront; the barrier in front of a position's window list keeps the list
+// of the position before it until its last reader is through.
+template <int U, int NT, int WV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WV, 8))) void k_film_chains(FilmRec F, BlockReplayArgs A, PatchArgs PA, uint32_t n_tiles, float *tiles,
+                  const uint32_t *__restrict__ chains, uint32_t n_chains) {
+    extern __shared__ float s_w[];
+    __shared__ unsigned short s_list[64];
+    const uint32_t tw = blockIdx.x / n_chains, chain = blockIdx.x % n_chains;
+    const uint32_t tile = tw * 64u + threadIdx.x;
+    const bool live = tile < n_tiles;
+    const BlockGeom g = block_geom(F, A.blocks_x, live ? (A.tile_list ? A.tile_list[tile] : tile) : 0u);
+    film_lanes_weights(A, s_w);
+    const uint32_t i0 = chains[chain], i1 = chains[chain + 1u];                    // (wave-uniform)
+    for (uint32_t i = i0; i < i1; ++i) {
+        const uint32_t pos = (uint32_t) __builtin_amdgcn_readfirstlane((int) chains[n_chains + 1u + i]);
+        __syncthreads();
+        film_lanes_block<U, NT>(F, A, tiles, tile, live, g, (int) (pos % PA.patches_x) * MIW_FL_BS, (int) (pos / PA.patches_x) * MIW_FL_BS, s_w, s_list);
+    }
 }
 
 // step 2: every film texel sums the block tiles covering it, ascending block id

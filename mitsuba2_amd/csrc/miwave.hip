@@ -73,6 +73,7 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "bvh4_build.h"
 #include "envmap_build.h"
 #include "film_classes.h"
+#include "film_chains.h"
 #include "lbvh_device.h"
 #include "sah_device.h"
 #include "bvh4_device.h"
@@ -188,6 +189,8 @@ static const KnobInfo g_knobs[] = {
     { "MIW_STREAM", "0: plan 1 walks with one kernel per list slice instead of the persistent stream kernel" },
     { "MIW_FILM_LEGACY", "1: the 24-byte position log + k_film_blocks for every filter" },
     { "MIW_FILM_LANES", "0 | 1 | 2: k_film_lanes off / over the tile-interleaved log / over [lane][sample]" },
+    { "MIW_FILM_CHAINS", "0: the replay over the tile-interleaved log runs k_film_lanes (a wavefront per block position) instead of k_film_chains (a wavefront per chain of positions of equal weight)" },
+    { "MIW_FILM_CHAINS_U", "4 | 8: records in flight per lane of k_film_chains: 8 (the default) compiled for two wavefronts per SIMD, 4 for three" },
     { "MIW_FILM_QUADS", "0 | 24 | 28 | 42 | 44: k_film_quads group shape (0: off)" },
     { "MIW_FILM_COLUMNS", "0 | 42 | 44 | 82: k_film_columns group shape" },
     { "MIW_FILM_GROUP", "2 | 3 | 4: k_film_groups group shape" },
@@ -270,6 +273,8 @@ struct mi_ctx {
     hipStream_t stream2[3] = { nullptr, nullptr, nullptr }; hipEvent_t ev_fork = nullptr, ev_join[3] = { nullptr, nullptr, nullptr };   // (kernels of ONE stream run one after the other: three replay streams)
     DevBuf<uint32_t> d_group_done, d_group_expected; uint32_t *h_group_flag = nullptr; uint32_t group_flag_cap = 0;
     std::vector<uint32_t> h_group_expected; std::vector<int32_t> h_block_tile;
+    // the chain table of k_film_chains (csrc/film_chains.h) and what it was built from: rebuilt and uploaded when one of them changes
+    DevBuf<uint32_t> d_film_chains; std::vector<uint32_t> h_film_chains; uint32_t film_chains_n = 0; int64_t film_chains_key = -1;
     int overlap_state = -1;             // -1: not tried; 0: the runtime refused (hipStreamWaitValue32 / the allocations); 1: available
     bool replay_enqueued = false;       // this frame's k_film_lanes launches already sit in the replay streams (assemble_film only joins)
     uint32_t replay_launches = 0;
@@ -330,7 +335,7 @@ void mi_destroy(mi_ctx *c) {
     c->q_tp.release(); c->q_res.release(); c->q_ray_o.release(); c->q_ray_d.release(); c->q_hit.release();
     c->q_sh_d.release(); c->q_sh_c.release(); c->q_st.release(); c->q_pos.release(); c->q_pixel.release(); c->q_sh_vis.release();
     c->d_accum.release(); c->d_out.release(); c->d_next_pixel.release(); c->d_lane_cost.release(); c->d_cost_sorted.release(); c->d_lane_iota.release(); c->d_lane_sorted.release(); c->d_place_tmp.release(); c->d_piece_list.release(); c->d_simd_ids.release(); c->d_lists.release(); c->d_list_counts.release(); c->d_block_ids.release(); c->d_tile_list.release(); c->d_cnt.release();
-    c->q_log_pos.release(); c->q_log_val.release(); c->q_log_rec.release(); c->d_fc_thr.release(); c->d_fc_w.release(); c->d_block_tile.release(); c->d_tiles.release();
+    c->q_log_pos.release(); c->q_log_val.release(); c->q_log_rec.release(); c->d_fc_thr.release(); c->d_fc_w.release(); c->d_block_tile.release(); c->d_tiles.release(); c->d_film_chains.release();
     for (hipEvent_t e : c->ev_pool) (void) hipEventDestroy(e);
     c->d_group_done.release(); c->d_group_expected.release(); c->d_sample_stage.release(); c->d_next_ray.release();
     if (c->h_group_flag) (void) hipHostFree(c->h_group_flag);
@@ -1494,7 +1499,7 @@ struct LaunchTimer {
 // ---- mi_render, phase "film plan": how ImageBlock::put is realised for this job (mi_render_cfg::film_mode), the sample log's record
 // format (16-byte class records where film_classes.h covers the filter, 24-byte positions otherwise), its layout ([lane][sample], or interleaved
 // over groups of 64 tiles for k_film_lanes) and its allocation ----
-struct FilmPlan { int film_mode = 0; bool rec16 = false; int film_lanes = 0; uint32_t log_il = 0; size_t log_entries = 0, rec_bytes = 0; };
+struct FilmPlan { int film_mode = 0; bool rec16 = false; int film_lanes = 0; bool film_chains = false; /* the replay outside the overlap route: k_film_chains */ uint32_t log_il = 0; size_t log_entries = 0, rec_bytes = 0; };
 static mi_status plan_film_log(mi_ctx *c, const mi_render_cfg *cfg, const Options &ropt, const RenderParams &P, hipStream_t s, int plan,
                                uint32_t n_tiles, uint32_t n_lanes, uint32_t bs2, uint32_t bs2_log2, size_t film_n, FilmPlan &FP) {
     (void) plan;
@@ -1569,7 +1574,7 @@ static mi_status plan_film_log(mi_ctx *c, const mi_render_cfg *cfg, const Option
     c->counters.log_record_bytes = film_mode == 1 ? (uint32_t) rec_bytes : 0u;
     c->counters.film_kernel = 0u; c->counters.log_interleaved = film_mode == 1 && rec16 && log_il ? 1u : 0u;
     c->counters.film_mode = (uint32_t) film_mode;
-    FP.film_mode = film_mode; FP.rec16 = rec16; FP.film_lanes = film_lanes; FP.log_il = log_il; FP.log_entries = log_entries; FP.rec_bytes = rec_bytes;
+    FP.film_mode = film_mode; FP.rec16 = rec16; FP.film_lanes = film_lanes; FP.film_chains = film_lanes == 1 && log_il != 0u && !ropt.off("MIW_FILM_CHAINS") && ropt.num("MIW_FL_NT", 1) != 0; FP.log_il = log_il; FP.log_entries = log_entries; FP.rec_bytes = rec_bytes;
     return MI_OK;
 }
 
@@ -1657,7 +1662,10 @@ static void print_debug_statistics(mi_ctx *c, const Options &ropt, mi_counters &
 
 // ---- mi_render, what every replay kernel is handed: the log, the pixel states, the class tables, the block -> tile map of this shard (uploaded from a
 // context-owned vector: nobody waits for that copy), the tile buffer ----
-struct FilmReplay { BlockReplayArgs A; uint32_t side = 0; uint32_t beside = 0; /* groups of 64 tiles replayed beside the path kernel (overlap_enqueue); the launch after it takes the rest */ };
+struct FilmReplay { BlockReplayArgs A; uint32_t side = 0; const uint32_t *chains = nullptr; uint32_t n_chains = 0; /* k_film_chains' table, where the replay takes it */ uint32_t beside = 0; /* groups of 64 tiles replayed beside the path kernel (overlap_enqueue); the launch after it takes the rest */ };
+#ifndef MIW_FILM_CHAINS_U_DEFAULT
+#define MIW_FILM_CHAINS_U_DEFAULT 8     /* records in flight per lane of k_film_chains: 8 at two wavefronts per SIMD replays C2 in 12.4 ms, 4 at three in 15.3 (k_film_lanes: 16.0) */
+#endif
 static mi_status film_replay_setup(mi_ctx *c, const mi_render_cfg *cfg, hipStream_t s, const FilmPlan &FP, uint32_t n_tiles, uint32_t bs, uint32_t bs2_log2,
                                    uint32_t blocks_x, uint32_t blocks_y, FilmReplay &R) {
     const bool rec16 = FP.rec16;
@@ -1676,6 +1684,18 @@ static mi_status film_replay_setup(mi_ctx *c, const mi_render_cfg *cfg, hipStrea
     R.side = bs + 2u * (uint32_t) cfg->filter_border;
     A.tile_stride = R.side * R.side * MIW_FILM_CHANNELS;
     HIP_TRY(c, c->d_tiles.resize((size_t) std::max<uint32_t>(n_tiles, 1) * A.tile_stride));
+    if (FP.film_chains) {
+        // the positions of a tile in chains of equal weight: a function of the tile's shape and the filter alone, so nearly every frame finds its table uploaded
+        const uint32_t patches = (R.side + MIW_FL_BS - 1) / MIW_FL_BS;
+        const int64_t key = (((int64_t) bs * 64 + cfg->filter_border) * 64 + c->classes.reach) * 4096 + patches;
+        if (key != c->film_chains_key) {
+            const miw_chains::Table t = miw_chains::build(patches, patches, MIW_FL_BS, (int) bs, cfg->filter_border, c->classes.reach);
+            c->h_film_chains = t.packed();                       // (nothing of an earlier frame is in flight: mi_render ends with a wait; the vector outlives the copy)
+            HIP_TRY(c, c->d_film_chains.upload(c->h_film_chains, s));
+            c->film_chains_n = t.chains(); c->film_chains_key = key;
+        }
+        R.chains = c->d_film_chains.p; R.n_chains = c->film_chains_n;
+    }
     return MI_OK;
 }
 
@@ -1844,7 +1864,17 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
                         // (the groups of 64 tiles below `first` were replayed beside the path kernel, on the replay streams: overlap_enqueue)
                         const uint32_t first = queued ? queued->beside : 0u, groups_all = ((uint32_t) n_tiles + 63u) / 64u;
                         const uint32_t waves_rest = (groups_all - first) * PC.patches_x * PC.patches_y;
+                        // round 11: outside the overlap route the positions of a tile are replayed in chains of equal weight (k_film_chains), with eight records
+                        // in flight per lane at two wavefronts per SIMD or (MIW_FILM_CHAINS_U=4) four at three
+                        const bool chains = !queued && R.chains != nullptr && R.n_chains != 0u;
+                        const int chains_u = ropt.num("MIW_FILM_CHAINS_U", MIW_FILM_CHAINS_U_DEFAULT) == 4 ? 4 : 8;
+                        if (ropt.get("MIW_DEBUG")) {
+                            if (chains) fprintf(stderr, "[miwave] film replay: k_film_chains, %u chains of %u positions per group of 64 tiles, %d records in flight per lane\n", R.n_chains, PC.patches_x * PC.patches_y, chains_u);
+                            else fprintf(stderr, "[miwave] film replay: k_film_lanes, %u positions per group of 64 tiles\n", PC.patches_x * PC.patches_y);
+                        }
                         if (waves_rest == 0u) { }
+                        else if (chains && chains_u == 8) MIW_TIMED(4, hipLaunchKernelGGL((k_film_chains<8, 1, 2>), dim3(groups_all * R.n_chains), dim3(64), lbytes, s, P.film, A, PC, (uint32_t) n_tiles, c->d_tiles.p, R.chains, R.n_chains));
+                        else if (chains) MIW_TIMED(4, hipLaunchKernelGGL((k_film_chains<4, 1, 3>), dim3(groups_all * R.n_chains), dim3(64), lbytes, s, P.film, A, PC, (uint32_t) n_tiles, c->d_tiles.p, R.chains, R.n_chains));
                         else if (fl_nt) MIW_TIMED(4, hipLaunchKernelGGL((k_film_lanes<4, 1>), dim3(waves_rest), dim3(64), lbytes, s, P.film, A, PC, (uint32_t) n_tiles, c->d_tiles.p, first, 0u));
                         else MIW_TIMED(4, hipLaunchKernelGGL((k_film_lanes<4, 0>), dim3(waves_rest), dim3(64), lbytes, s, P.film, A, PC, (uint32_t) n_tiles, c->d_tiles.p, first, 0u));
                         if (queued) { for (int i = 0; i < 3; ++i) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join[i], 0)); }
