@@ -1335,6 +1335,13 @@ static_assert(miw_pick::ALL == MATS_ALL && miw_pick::DIFFUSE == MATS_DIFFUSE && 
 // (resident_kernel.h; kernel_pick.h: frame_twin): the lean twin with the facts of a full frame's launch compiled in.
 #define MIW_LEAN_LIST(X) X(2, MATS_DIFFUSE) X(1, MATS_DIFFUSE) X(2, MATS_PLAIN) X(1, MATS_PLAIN)
 #define MIW_PICKED(T, M, A) (pick.tiny == (T) && pick.mats == (M) && pick.analytic == (A))
+// MIW_DEBUG: every launch of a path kernel says on stderr which instantiation it is, "[miwave] kernel launched: NAME<ARG, ARG, ...>" with the template arguments as
+// the launch site spells them. The text is the launch macro's own arguments, stringified beside the launch: it cannot name another kernel than
+// the one launched. tests/test_instantiation_census_gpu.py reads these lines; tests/instantiation_cases.py is keyed by them.
+// MIW_LAUNCH_NAMED launches `kernel_` — the template-id in parentheses, as hipLaunchKernelGGL takes it — and prints that very text (without the parentheses).
+#define MIW_SAY_KERNEL_TEXT(opt_, text_) do { if ((opt_).get("MIW_DEBUG")) fprintf(stderr, "[miwave] kernel launched: %s\n", text_); } while (0)
+#define MIW_LAUNCH_NAMED(opt_, kernel_, ...) do { if ((opt_).get("MIW_DEBUG")) fprintf(stderr, "[miwave] kernel launched: %.*s\n", (int) sizeof(#kernel_) - 3, #kernel_ + 1); \
+    hipLaunchKernelGGL(kernel_, __VA_ARGS__); } while (0)
 
 // the scene facts the rules read, from the context and the options of this call
 static miw_pick::Facts pick_facts(const mi_ctx *c, const Options &opt) {
@@ -1364,7 +1371,7 @@ static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO 
     const miw_pick::Facts facts = pick_facts(c, c->opt);
     const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, true);
     const uint32_t integ = direct ? INTEG_DIRECT : INTEG_PATH;
-#define MIW_SAMPLE_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) hipLaunchKernelGGL((k_sample_rays<T, M, A, I>), grid, block, c->lds_bytes, s, P, c->view, io, c->lds_cfg, c->d_next_ray.p); else
+#define MIW_SAMPLE_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_LAUNCH_NAMED(c->opt, (k_sample_rays<T, M, A, I>), grid, block, c->lds_bytes, s, P, c->view, io, c->lds_cfg, c->d_next_ray.p); else
     MIW_SAMPLE_LIST(MIW_SAMPLE_LAUNCH) return fail(c, MI_ERR_STATE, "mi_sample: no k_sample_rays<%d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_SAMPLE_LAUNCH
     HIP_TRY(c, hipGetLastError());
@@ -2344,7 +2351,9 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 // (the interior's shade runs are long: loops that wait for them less often win there). MIW_LOOP_EXIT=node:triangle overrides.
                 ph_cfg.node_exit = c->have_env ? 2u : 1u; ph_cfg.tri_exit = c->have_env ? 3u : 2u;
                 if (const char *e = ropt.get("MIW_LOOP_EXIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a >= 0 && b >= 0) { ph_cfg.node_exit = (uint32_t) a; ph_cfg.tri_exit = (uint32_t) b; } }
-#define MIW_PHASED_LAUNCH_(M, A, WV, W, PL) MIW_TIMED(6, hipLaunchKernelGGL((k_path_phased<M, A, MIW_PHASE_SPEC != 0, WV, W, PL>), phgrid, block, rlds, s, P, (W) == 2 ? view8 : c->view, Q, c->d_cnt.p, ph_cfg, end, c->d_next_pixel.p))
+// (the Spec argument is a constant of the build, phased_kernel.h: MIW_DEBUG's line gives its value, the other five arguments as the macro got them)
+#define MIW_PHASED_LAUNCH_(M, A, WV, W, PL) do { MIW_SAY_KERNEL_TEXT(ropt, MIW_PHASE_SPEC != 0 ? "k_path_phased<" #M ", " #A ", true, " #WV ", " #W ", " #PL ">" : "k_path_phased<" #M ", " #A ", false, " #WV ", " #W ", " #PL ">"); \
+    MIW_TIMED(6, hipLaunchKernelGGL((k_path_phased<M, A, MIW_PHASE_SPEC != 0, WV, W, PL>), phgrid, block, rlds, s, P, (W) == 2 ? view8 : c->view, Q, c->d_cnt.p, ph_cfg, end, c->d_next_pixel.p)); } while (0)
 #define MIW_PHASED_LAUNCH(M, A, W) do { if (ph_waves == 4) MIW_PHASED_LAUNCH_(M, A, 4, W, false); else MIW_PHASED_LAUNCH_(M, A, 3, W, false); } while (0)
                 K.tree_width = phased ? (phased8 ? 8u : (c->view.nodes4 ? 4u : 2u)) : 0u;
 #if MIW_SPECTRAL
@@ -2366,7 +2375,7 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     const miw_pick::Pick pick = miw_pick::tree_class(facts);
 #define MIW_POOLED_LAUNCH(M, A, NW_, PP_) if (pick.mats == (M) && pick.analytic == (A) && pool_nw == (NW_) && pool_pp == (PP_)) { \
                         HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
-                        MIW_TIMED(6, hipLaunchKernelGGL((k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } else
+                        MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } else
                     MIW_POOLED_LIST(MIW_POOLED_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_pooled<%d, %d, %d, %d> in the library", pick.mats, (int) pick.analytic, pool_nw, pool_pp);
 #undef MIW_POOLED_LAUNCH
                     K.pooled = 1u; K.pool_waves = (uint32_t) pool_nw;
@@ -2384,17 +2393,20 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                 }
 #undef MIW_PHASED_LAUNCH
 #undef MIW_PHASED_LAUNCH_
+                // (MIW_DEBUG's line is the text of the template-id the launch instantiates: MIW_LAUNCH_NAMED)
+#define MIW_PACKET_SPECIAL(...) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (__VA_ARGS__), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
                 // the special instantiations of the packet kernel, in front of its table (none of them is ever the direct integrator's: `overlap` and `packet_shard4` above)
                 else if (Q.group_done && c->view.tri_count <= 32u)     // (overlap: tiny && diffuse_only) the instantiation that counts finished pixels per group of 64 tiles
-                    MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>);
                 else if (Q.group_done)
-                    MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                    MIW_PACKET_SPECIAL(k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>);
                 else if (packet_shard4 && !Q.group_done && feat == FEAT_NONE) {
                     feat_launched = FEAT_NONE;
-                    MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4, FEAT_NONE>);
                 }
                 else if (packet_shard4 && !Q.group_done)
-                    MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p));
+                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>);
+#undef MIW_PACKET_SPECIAL
                 else {
                     // kernel variants (kernel_pick.h): no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that variant fits 4 waves per
                     // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
@@ -2406,20 +2418,20 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
                     lf.job_chunks = Q.job_chunk != 0u; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = rcfg.queues == 1u; lf.tail_prio = rcfg.tail_prio != 0u;
                     lf.leaf_filter = c->lds_cfg.leaves != 0u; lf.group_counts = Q.group_done != nullptr;
                     const bool frame = miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
-#define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
+#define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
                     MIW_LEAN_LIST(MIW_FRAME_LAUNCH)
 #undef MIW_FRAME_LAUNCH
-#define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
+#define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
                     MIW_LEAN_LIST(MIW_LEAN_LAUNCH)
 #undef MIW_LEAN_LAUNCH
-#define MIW_RESIDENT_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<true, T, M, A, I>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); else
+#define MIW_RESIDENT_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, A, I>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); else
                     MIW_RESIDENT_LIST(MIW_RESIDENT_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<true, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_RESIDENT_LAUNCH
                 }
             } else {
                 // the float64-atomics film: one workgroup per 16 x 16 pixels, three classes (kernel_pick.h: resident_atomic)
                 const miw_pick::Pick pick = miw_pick::resident_atomic(facts);
-#define MIW_ATOMIC_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, hipLaunchKernelGGL((k_path_resident<false, T, M, A, I>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr)); else
+#define MIW_ATOMIC_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<false, T, M, A, I>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr)); else
                 MIW_ATOMIC_LIST(MIW_ATOMIC_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<false, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_ATOMIC_LAUNCH
             }

@@ -225,20 +225,11 @@ def test_render_and_sample_agree_except_for_the_trio_tree_kernel(picks):
 
 def test_every_pick_is_in_its_list():
     """the lists of instantiations (miwave.hip: MIW_*_LIST) hold every tuple a rule can return: a pick outside is MI_ERR_STATE at run time"""
-    import re
-    src = open(ROOT + "/mitsuba2_amd/csrc/miwave.hip").read()
-    names = dict(MATS_ALL=ALL, MATS_DIFFUSE=DIFFUSE, MATS_PLAIN=PLAIN, MATS_TRIO=TRIO, MATS_NESTED=NESTED, MATS_LIGHTS=LIGHTS)
-
-    def body(name):
-        m = re.search(r"#define %s\(X(?:, \.\.\.)?\)((?:.*\\\n)*.*)\n" % name, src)
-        return re.sub(r"/\*.*?\*/", "", m.group(1))
-
-    def tuples(name):
-        return {(int(t), names[m], a == "true", i) for t, m, a, i in re.findall(r"X\((\d), (MATS_[A-Z]+), (true|false), (INTEG_[A-Z]+)\)", body(name))}
-
-    path, direct, atomic = tuples("MIW_PATH_TUPLES"), tuples("MIW_DIRECT_TUPLES"), tuples("MIW_ATOMIC_LIST")
+    import kernel_lists as K                                      # (the list parser, shared with test_instantiation_census.py)
+    src = K.source()
+    path, direct, atomic = K.tuples(src, "MIW_PATH_TUPLES"), K.tuples(src, "MIW_DIRECT_TUPLES"), K.tuples(src, "MIW_ATOMIC_LIST")
     assert len(path) == 12 and len(direct) == 8 and len(atomic) == 12
-    tree = {(names[m], a == "true") for m, a in re.findall(r"X\((MATS_[A-Z]+), (true|false), __VA_ARGS__\)", body("MIW_TREE_CLASSES"))}
+    tree = K.tree_classes(src)
     assert len(tree) == 6
     for b in range(512):
         f = F(b)
