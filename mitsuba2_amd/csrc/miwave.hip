@@ -74,6 +74,7 @@ __device__ __forceinline__ unsigned long long *miw_sec_buf() { __shared__ unsign
 #include "envmap_build.h"
 #include "film_classes.h"
 #include "film_chains.h"
+#include "render_plan.h"
 #include "lbvh_device.h"
 #include "sah_device.h"
 #include "bvh4_device.h"
@@ -293,6 +294,7 @@ static mi_status fail(mi_ctx *c, mi_status code, const char *fmt, ...) {
 }
 #define HIP_TRY(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return fail(c, MI_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#define MI_TRY(expr) do { const mi_status st_ = (expr); if (st_ != MI_OK) return st_; } while (0)   /* a phase that failed has said why (fail) */
 
 static thread_local std::string g_global_error;
 
@@ -728,10 +730,6 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
 // ---- BVH build ------------------------------------------------------------------------
 // dwords of the tables stage_tables() copies into LDS (shapes, bsdfs, emitters, emit_tri, emit_vnorm, emit_pmf, emit_cdf), each
 // padded to 16 bytes; returns the bytes of the block
-#define MIW_LDS_PER_CU (160u * 1024u)
-#define MIW_LDS_PER_WORKGROUP (MIW_LDS_PER_CU / 4u) /* 160 KB per CU / four workgroups of 256 (four wavefronts per SIMD) */
-#define MIW_LDS_STATIC 1024u                      /* static __shared__ of k_path_phased and of the packet kernels: s_job_pend (QueueWork: a word per lane); s_prog, 16 bytes, inside the granule below */
-#define MIW_LDS_GRANULE 512u                      /* LDS is handed out in granules: dynamic + static, rounded up, must stay inside 40 KB */
 static size_t lds_table_bytes(const mi_ctx *c, uint32_t words[12], bool with_tris) {
     words[0] = (uint32_t) (c->shapes.size() * sizeof(ShapeRec) / 4); words[1] = (uint32_t) (c->bsdfs.size() * sizeof(BsdfRec) / 4);
     words[2] = (uint32_t) (c->emitters.size() * sizeof(EmitterRec) / 4);
@@ -1502,14 +1500,36 @@ struct LaunchTimer {
         stamps.clear(); ev_used = 0;
     }
 };
+// a launch on the stream `s` between two events of the timer `T` (both, and the context `c`, by those names where the macro is used)
+#define MIW_TIMED(cls_, launch) do {                                                   \
+        size_t e0_ = 0, e1_ = 0;                                                       \
+        if (T.on) { HIP_TRY(c, T.get_event(e0_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e0_], s)); } \
+        launch;                                                                        \
+        if (T.on) { HIP_TRY(c, T.get_event(e1_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e1_], s)); \
+                    T.stamps.push_back({ cls_, e0_, e1_ }); }                          \
+    } while (0)
 
 // ---- mi_render, phase "film plan": how ImageBlock::put is realised for this job (mi_render_cfg::film_mode), the sample log's record
 // format (16-byte class records where film_classes.h covers the filter, 24-byte positions otherwise), its layout ([lane][sample], or interleaved
 // over groups of 64 tiles for k_film_lanes) and its allocation ----
 struct FilmPlan { int film_mode = 0; bool rec16 = false; int film_lanes = 0; bool film_chains = false; /* the replay outside the overlap route: k_film_chains */ uint32_t log_il = 0; size_t log_entries = 0, rec_bytes = 0; };
-static mi_status plan_film_log(mi_ctx *c, const mi_render_cfg *cfg, const Options &ropt, const RenderParams &P, hipStream_t s, int plan,
-                               uint32_t n_tiles, uint32_t n_lanes, uint32_t bs2, uint32_t bs2_log2, size_t film_n, FilmPlan &FP) {
-    (void) plan;
+// ---- mi_render, what every phase reads: the job, this render's options and parameters, the frame's geometry (frame_geometry), the execution plan,
+// the film plan, the lane queues as the kernels get them, the launch timer and the counters ----
+struct RenderFrame {
+    mi_ctx *c; const mi_render_cfg *cfg;
+    Options ropt;                                                 // the context's options under the job's debug overrides (render_options)
+    RenderParams P; hipStream_t s = nullptr;
+    uint32_t bs = 0, bs2 = 0, bs2_log2 = 0, blocks_x = 0, blocks_y = 0, n_tiles = 0, n_lanes = 0; size_t film_n = 0;
+    int plan = 0;                                                 // 1: wavefront (queue) plan, 2: resident plan
+    FilmPlan FP; LaneQueues Q;
+    LaunchTimer T;                                                // HIP-event time per launch class (mi_counters::ms_*)
+    mi_counters &K;
+    std::chrono::steady_clock::time_point wall0;
+    RenderFrame(mi_ctx *c_, const mi_render_cfg *cfg_) : c(c_), cfg(cfg_), ropt(c_->opt), T{ c_, c_->counters, cfg_->profile != 0 }, K(c_->counters) {}
+};
+static mi_status plan_film_log(RenderFrame &F) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s;
+    const uint32_t n_tiles = F.n_tiles, n_lanes = F.n_lanes, bs2 = F.bs2, bs2_log2 = F.bs2_log2; const size_t film_n = F.film_n; FilmPlan &FP = F.FP;
     // film mode: sample log + ordered gather if the log fits, else float64 atomics
     int film_mode = cfg->film_mode;
     const size_t nl = std::max<uint32_t>(n_lanes, 1);
@@ -1573,7 +1593,7 @@ static mi_status plan_film_log(mi_ctx *c, const mi_render_cfg *cfg, const Option
     {
         auto poison = [&](void *p, size_t bytes) -> hipError_t { return p && bytes ? hipMemsetAsync(p, 0xff, bytes, s) : hipSuccess; };
         HIP_TRY(c, poison(c->q_log_rec.p, c->q_log_rec.n * sizeof(U4))); HIP_TRY(c, poison(c->q_log_pos.p, c->q_log_pos.n * sizeof(F2))); HIP_TRY(c, poison(c->q_log_val.p, c->q_log_val.n * sizeof(F4)));
-        if (plan == 1) for (DevBuf<F4> *q : { &c->q_tp, &c->q_res, &c->q_ray_o, &c->q_ray_d, &c->q_hit, &c->q_sh_d, &c->q_sh_c }) HIP_TRY(c, poison(q->p, q->n * sizeof(F4)));
+        if (F.plan == 1) for (DevBuf<F4> *q : { &c->q_tp, &c->q_res, &c->q_ray_o, &c->q_ray_d, &c->q_hit, &c->q_sh_d, &c->q_sh_c }) HIP_TRY(c, poison(q->p, q->n * sizeof(F4)));
         HIP_TRY(c, poison(c->d_tiles.p, c->d_tiles.n * sizeof(float)));
     }
 #endif
@@ -1673,8 +1693,9 @@ struct FilmReplay { BlockReplayArgs A; uint32_t side = 0; const uint32_t *chains
 #ifndef MIW_FILM_CHAINS_U_DEFAULT
 #define MIW_FILM_CHAINS_U_DEFAULT 8     /* records in flight per lane of k_film_chains: 8 at two wavefronts per SIMD replays C2 in 12.4 ms, 4 at three in 15.3 (k_film_lanes: 16.0) */
 #endif
-static mi_status film_replay_setup(mi_ctx *c, const mi_render_cfg *cfg, hipStream_t s, const FilmPlan &FP, uint32_t n_tiles, uint32_t bs, uint32_t bs2_log2,
-                                   uint32_t blocks_x, uint32_t blocks_y, FilmReplay &R) {
+static mi_status film_replay_setup(RenderFrame &F, FilmReplay &R) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; hipStream_t s = F.s; const FilmPlan &FP = F.FP;
+    const uint32_t n_tiles = F.n_tiles, bs = F.bs, bs2_log2 = F.bs2_log2, blocks_x = F.blocks_x, blocks_y = F.blocks_y;
     const bool rec16 = FP.rec16;
     std::vector<int32_t> &block_tile = c->h_block_tile;
     block_tile.assign(cfg->block_count, -1);
@@ -1717,7 +1738,9 @@ __global__ void k_raise_flags(uint32_t *flag, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) __hip_atomic_store(flag + i, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-static mi_status overlap_prepare(mi_ctx *c, const mi_render_cfg *cfg, hipStream_t s, uint32_t n_tiles, uint32_t bs, uint32_t blocks_x, LaneQueues &Q, uint32_t bs2_log2) {
+static mi_status overlap_prepare(RenderFrame &F) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; hipStream_t s = F.s; LaneQueues &Q = F.Q;
+    const uint32_t n_tiles = F.n_tiles, bs = F.bs, blocks_x = F.blocks_x, bs2_log2 = F.bs2_log2;
     const uint32_t n_groups = (n_tiles + 63u) / 64u;
     if (!c->ev_fork) {
         bool ok = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) == hipSuccess;
@@ -1748,7 +1771,8 @@ static mi_status overlap_prepare(mi_ctx *c, const mi_render_cfg *cfg, hipStream_
     return MI_OK;
 }
 // after the path kernel has been launched on `s`: fork, the waits + launches on stream2, the release-all behind the path kernel, the join event
-static mi_status overlap_enqueue(mi_ctx *c, const Options &ropt, const RenderParams &P, hipStream_t s, LaunchTimer &T, FilmReplay &R, uint32_t n_tiles, bool wait_flags) {
+static mi_status overlap_enqueue(RenderFrame &F, FilmReplay &R, bool wait_flags) {
+    mi_ctx *c = F.c; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s; LaunchTimer &T = F.T; const uint32_t n_tiles = F.n_tiles;
     const uint32_t n_all = (n_tiles + 63u) / 64u;
     // how many groups are replayed BESIDE the path kernel; the rest in one launch after it (assemble_film). What runs after it cannot take less than one
     // wavefront's chain (~8 - 10 ms) however little it is; measured at C2 (gpurun r6m): three quarters beside 263.6 ms, half 266.1, none 265.8
@@ -1803,18 +1827,11 @@ static mi_status overlap_enqueue(mi_ctx *c, const Options &ropt, const RenderPar
 
 // ---- mi_render, phase "film": the ordered replay of the sample log into block tiles (device/film_kernels.h; which kernel: the log
 // format, the shard's tile count, the options) + the merge of the tiles into the film, or the resolve of the float64 sums ----
-static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Options &ropt, const RenderParams &P, hipStream_t s, LaunchTimer &T, const FilmPlan &FP,
-                               uint32_t n_tiles, uint32_t bs, uint32_t bs2_log2, uint32_t blocks_x, uint32_t blocks_y, size_t film_n, void *film, mi_status result,
-                               const FilmReplay *queued /* != nullptr: the replay's launches already sit in stream2 (overlap_enqueue) */) {
-    const int film_mode = FP.film_mode; const bool rec16 = FP.rec16; const int film_lanes = FP.film_lanes; const uint32_t log_il = FP.log_il;
+static mi_status assemble_film(RenderFrame &F, void *film, mi_status result, const FilmReplay *queued /* != nullptr: the replay's launches already sit in stream2 (overlap_enqueue) */) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s; LaunchTimer &T = F.T;
+    const uint32_t n_tiles = F.n_tiles; const size_t film_n = F.film_n;
+    const int film_mode = F.FP.film_mode; const bool rec16 = F.FP.rec16; const int film_lanes = F.FP.film_lanes;
     (void) result;
-#define MIW_TIMED(cls_, launch) do {                                                   \
-        size_t e0_ = 0, e1_ = 0;                                                       \
-        if (T.on) { HIP_TRY(c, T.get_event(e0_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e0_], s)); } \
-        launch;                                                                        \
-        if (T.on) { HIP_TRY(c, T.get_event(e1_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e1_], s)); \
-                    T.stamps.push_back({ cls_, e0_, e1_ }); }                          \
-    } while (0)
     {
         const size_t elem = cfg->film_f64 ? sizeof(double) : sizeof(float);
         void *dst = film;
@@ -1828,7 +1845,7 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
         if (film_mode == 1) {
             FilmReplay R;
             if (queued) R = *queued;                              // (set up before the path kernel was launched)
-            else { const mi_status rs = film_replay_setup(c, cfg, s, FP, n_tiles, bs, bs2_log2, blocks_x, blocks_y, R); if (rs != MI_OK) return rs; }
+            else MI_TRY(film_replay_setup(F, R));
             BlockReplayArgs &A = R.A;
             const uint32_t side = R.side;
             if (n_tiles) {
@@ -1926,15 +1943,11 @@ static mi_status assemble_film(mi_ctx *c, const mi_render_cfg *cfg, const Option
         }
 #endif
     }
-#undef MIW_TIMED
     return MI_OK;
 }
 
-mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
-    if (!c || !cfg || !film) return MI_ERR_INVALID;
-    if (!c->have_bvh) return fail(c, MI_ERR_STATE, "mi_render: call mi_scene_upload and mi_bvh_build first");
-    // this render's options: the context's, under the job's debug overrides (include/miwave.h: mi_render_cfg::debug_*)
-    Options ropt = c->opt;
+// ---- mi_render, phase "options": this render's options — the context's, under the job's debug overrides (include/miwave.h: mi_render_cfg::debug_*) ----
+static mi_status render_options(mi_ctx *c, const mi_render_cfg *cfg, Options &ropt) {
     switch (cfg->debug_film_replay) {
         case MI_FILM_REPLAY_AUTO: break;
         case MI_FILM_REPLAY_BLOCKS: ropt.v["MIW_FILM_LEGACY"] = "1"; break;
@@ -1955,9 +1968,14 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         case MI_PATH_KERNEL_POOLED: ropt.v.erase("MIW_PHASED"); ropt.v["MIW_POOLED"] = "1"; break;
         default: return fail(c, MI_ERR_INVALID, "render: debug_path_kernel must be one of MI_PATH_KERNEL_*");
     }
-    RenderParams P;
-    mi_status st = fill_params(c, cfg, P);
-    if (st != MI_OK) return st;
+    return MI_OK;
+}
+
+// ---- mi_render, phase "geometry": the job's parameters (fill_params), its validation, the sizes derived from it — blocks, tiles, lanes, film values —
+// and the execution plan (mi_render_cfg::plan 0: chosen here) with the refusals of what only the resident plan serves ----
+static mi_status frame_geometry(RenderFrame &F) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; RenderParams &P = F.P;
+    MI_TRY(fill_params(c, cfg, P));
     const uint32_t bs = (uint32_t) cfg->block_size, bs2 = bs * bs;
     uint32_t bs2_log2 = 0; while ((1u << bs2_log2) < bs2) ++bs2_log2;
     const uint32_t blocks_x = (cfg->crop_w + bs - 1) / bs, blocks_y = (cfg->crop_h + bs - 1) / bs;
@@ -1971,11 +1989,12 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     if (n_lanes64 >= (1ull << 31)) return fail(c, MI_ERR_INVALID, "render: too many lanes");
     const uint32_t n_lanes = (uint32_t) n_lanes64;
     P.n_lanes = n_lanes;
-    const size_t film_n = (size_t) cfg->crop_w * cfg->crop_h * MIW_FILM_CHANNELS;
+    F.bs = bs; F.bs2 = bs2; F.bs2_log2 = bs2_log2; F.blocks_x = blocks_x; F.blocks_y = blocks_y; F.n_tiles = n_tiles; F.n_lanes = n_lanes;
+    F.film_n = (size_t) cfg->crop_w * cfg->crop_h * MIW_FILM_CHANNELS;
 
     HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    auto wall0 = std::chrono::steady_clock::now();
+    F.s = c->stream;
+    F.wall0 = std::chrono::steady_clock::now();
     c->cancel.store(0);
 
     // execution plan
@@ -1991,14 +2010,20 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     if (cfg->plan == 1) return fail(c, MI_ERR_INVALID, "render: the scalar_spectral library runs the resident plan only (plan 0 or 2)");
     plan = 2;
 #endif
-    const bool direct = P.integrator == INTEG_DIRECT;
-    const uint32_t integ = direct ? INTEG_DIRECT : INTEG_PATH;
-    if (direct) {                                                // direct.h runs on the paired query of the resident plan
+    if (P.integrator == INTEG_DIRECT) {                          // direct.h runs on the paired query of the resident plan
         if (cfg->plan == 1) return fail(c, MI_ERR_INVALID, "render: the direct integrator runs the resident plan only (plan 0 or 2)");
         plan = 2;
     }
     c->counters.plan = (uint32_t) plan;
+    F.plan = plan;
+    return MI_OK;
+}
 
+// ---- mi_render, phase "queues": the per-lane state of the plan, the film plan with its log (plan_film_log), the block and tile lists on the device,
+// and the lane queues as the kernels get them ----
+static mi_status frame_queues(RenderFrame &F) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; hipStream_t s = F.s; LaneQueues &Q = F.Q;
+    const int plan = F.plan; const uint32_t n_lanes = F.n_lanes, n_tiles = F.n_tiles;
     size_t nl = std::max<uint32_t>(n_lanes, 1);
     HIP_TRY(c, c->q_st.resize(nl)); HIP_TRY(c, c->q_pixel.resize(nl));
     if (plan == 1) {
@@ -2010,10 +2035,8 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
     HIP_TRY(c, hipMemsetAsync(c->d_cnt.p, 0, sizeof(Counters) * MIW_CNT_SHARDS, s));
 
     // film mode: sample log + ordered gather if the log fits, else float64 atomics; the log's format and layout follow the replay kernel
-    FilmPlan FP;
-    FilmReplay replay;                                            // (filled before the path kernel when the replay is queued beside it)
-    { const mi_status fs = plan_film_log(c, cfg, ropt, P, s, plan, n_tiles, n_lanes, bs2, bs2_log2, film_n, FP); if (fs != MI_OK) return fs; }
-    const int film_mode = FP.film_mode; const bool rec16 = FP.rec16; const int film_lanes = FP.film_lanes; const uint32_t log_il = FP.log_il;
+    MI_TRY(plan_film_log(F));
+    const int film_mode = F.FP.film_mode; const bool rec16 = F.FP.rec16; const uint32_t log_il = F.FP.log_il;
     HIP_TRY(c, c->d_block_ids.resize(cfg->block_count));
     HIP_TRY(c, hipMemcpyAsync(c->d_block_ids.p, cfg->block_ids, cfg->block_count * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (cfg->tile_list && n_tiles) {
@@ -2021,73 +2044,81 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         HIP_TRY(c, hipMemcpyAsync(c->d_tile_list.p, cfg->tile_list, n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     }
 
-    LaneQueues Q;
     Q.tp = c->q_tp.p; Q.res = c->q_res.p; Q.st = c->q_st.p; Q.pos = c->q_pos.p; Q.pixel = c->q_pixel.p;
     Q.ray_o = c->q_ray_o.p; Q.ray_d = c->q_ray_d.p; Q.hit = c->q_hit.p;
     Q.sh_d = c->q_sh_d.p; Q.sh_c = c->q_sh_c.p; Q.sh_vis = c->q_sh_vis.p;
     Q.log_pos = film_mode == 1 && !rec16 ? c->q_log_pos.p : nullptr; Q.log_val = film_mode == 1 && !rec16 ? c->q_log_val.p : nullptr;
     Q.lane_cost = nullptr; Q.lane_sorted = nullptr; Q.piece_list = nullptr; Q.simd_ids = nullptr; Q.piece_a = 64u; Q.piece_b = 1u;
     Q.log_rec = film_mode == 1 && rec16 ? c->q_log_rec.p : nullptr; Q.log_thr = rec16 ? c->d_fc_thr.p : nullptr; Q.log_rej = rec16 ? c->classes.count | ((film_mode == 1 ? log_il : 0u) << 8) : 0u;
-    // ---- dynamic LDS of the render launches: [staged geometry | per-lane stack][256 phase thresholds (16-byte records)][the scene's
-    // small tables + the environment warp's smallest levels (trace.h: stage_tables)]. The kernels that stage the tables keep four
-    // workgroups per CU (160 KB / 4), so everything has to fit 40 KB less one allocation granule; a scene whose tables do not takes
-    // the lock-step tree kernels, which read them from global memory (tables_fit; mi_bvh_build applies the same bound before it
-    // declares a scene tiny). The 8-wide walk's stack is one 8-byte entry per LEVEL of its tree (miw/bvh8.h): a launch that will
-    // run it sizes the column by the tree's depth instead of the 4-wide walk's 32 x 4 bytes, and the bytes that frees go to more
-    // levels of the environment warp (round 5: the 0.9 M-triangle interior, depth 10 -> 20 KB of stack, warp levels down to 64 x 32).
-    struct LdsLayout { TraceLds cfg; size_t rlds, rlds_plain, table_bytes; bool tables_fit; };
-    const size_t lds_budget4 = MIW_LDS_PER_WORKGROUP - MIW_LDS_STATIC - MIW_LDS_GRANULE;
-    auto lay_out = [&](size_t base, size_t env_cap, size_t lds_budget) {
-        LdsLayout L; L.cfg = c->lds_cfg; L.rlds = base;
-        L.cfg.thr16 = (uint32_t) ((L.rlds + 15) / 16);
-        if (rec16) L.rlds = (size_t) L.cfg.thr16 * 16 + (MIW_FC_TABLE + 3) / 4 * 16;
-        L.cfg.tab16 = (uint32_t) ((L.rlds + 15) / 16);
-        L.table_bytes = lds_table_bytes(c, L.cfg.tab_words, c->lds_cfg.brute != 0);
-        L.cfg.light_words = (uint32_t) (c->lights.size() * sizeof(LightRec) / 4);
-        // (packet scenes always stage: mi_bvh_build bounded their tables by 24 KB, which with the packets, boxes and thresholds stays
-        // inside the 64 KB a workgroup may ask for, less the kernels' static __shared__ and a granule — at fewer workgroups per CU past
-        // what lds_workgroups() below allows)
-        L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u - MIW_LDS_STATIC - MIW_LDS_GRANULE : lds_budget);
-        L.cfg.env_top_count = L.cfg.env_top_base = L.cfg.env_top_words = 0;
-        if (L.tables_fit && c->have_env && !ropt.off("MIW_ENV_TOP")) {
-            // ... and as many of the environment warp's smallest levels as fit what is left (at most env_cap): levels are stored from
-            // the largest (0) to the smallest (n_levels - 1), so the top `count` levels are the tail of the array
-            const EnvmapRec &e = c->env_host;
-            const size_t used = (size_t) L.cfg.tab16 * 16 + L.table_bytes;
-            const size_t room = used < lds_budget ? std::min<size_t>(env_cap, lds_budget - used) : 0;
-            uint32_t count = 0;
-            while (count + 1 < e.n_levels && ((size_t) c->env_levels_total - e.level_offset[e.n_levels - 1 - count]) * 4 <= room) ++count;
-            if (count) {
-                L.cfg.env_top_count = count; L.cfg.env_top_base = e.level_offset[e.n_levels - count];
-                L.cfg.env_top_words = (uint32_t) (c->env_levels_total - L.cfg.env_top_base);
-                L.table_bytes += ((size_t) L.cfg.env_top_words + 3) / 4 * 16;
-            }
+    return MI_OK;
+}
+
+// ---- mi_render, phase "LDS layout" ----
+// dynamic LDS of the render launches: [staged geometry | per-lane stack][256 phase thresholds (16-byte records)][the scene's
+// small tables + the environment warp's smallest levels (trace.h: stage_tables)]. The kernels that stage the tables keep four
+// workgroups per CU (160 KB / 4), so everything has to fit 40 KB less one allocation granule; a scene whose tables do not takes
+// the lock-step tree kernels, which read them from global memory (tables_fit; mi_bvh_build applies the same bound before it
+// declares a scene tiny). The 8-wide walk's stack is one 8-byte entry per LEVEL of its tree (miw/bvh8.h): a launch that will
+// run it sizes the column by the tree's depth instead of the 4-wide walk's 32 x 4 bytes, and the bytes that frees go to more
+// levels of the environment warp (round 5: the 0.9 M-triangle interior, depth 10 -> 20 KB of stack, warp levels down to 64 x 32).
+struct LdsLayout { TraceLds cfg; size_t rlds, rlds_plain, table_bytes; bool tables_fit; };
+// one layout: `base` bytes of staged geometry or stacks in front, at most `env_cap` bytes of environment warp levels, everything inside `lds_budget`
+static LdsLayout lds_layout(const mi_ctx *c, const Options &ropt, bool rec16, size_t base, size_t env_cap, size_t lds_budget) {
+    LdsLayout L; L.cfg = c->lds_cfg; L.rlds = base;
+    L.cfg.thr16 = (uint32_t) ((L.rlds + 15) / 16);
+    if (rec16) L.rlds = (size_t) L.cfg.thr16 * 16 + (MIW_FC_TABLE + 3) / 4 * 16;
+    L.cfg.tab16 = (uint32_t) ((L.rlds + 15) / 16);
+    L.table_bytes = lds_table_bytes(c, L.cfg.tab_words, c->lds_cfg.brute != 0);
+    L.cfg.light_words = (uint32_t) (c->lights.size() * sizeof(LightRec) / 4);
+    // (packet scenes always stage: mi_bvh_build bounded their tables by 24 KB, which with the packets, boxes and thresholds stays
+    // inside the 64 KB a workgroup may ask for, less the kernels' static __shared__ and a granule — at fewer workgroups per CU past
+    // what lds_workgroups() below allows)
+    L.tables_fit = (size_t) L.cfg.tab16 * 16 + L.table_bytes <= (c->lds_cfg.brute ? 64u * 1024u - MIW_LDS_STATIC - MIW_LDS_GRANULE : lds_budget);
+    L.cfg.env_top_count = L.cfg.env_top_base = L.cfg.env_top_words = 0;
+    if (L.tables_fit && c->have_env && !ropt.off("MIW_ENV_TOP")) {
+        // ... and as many of the environment warp's smallest levels as fit what is left (at most env_cap): levels are stored from
+        // the largest (0) to the smallest (n_levels - 1), so the top `count` levels are the tail of the array
+        const EnvmapRec &e = c->env_host;
+        const size_t used = (size_t) L.cfg.tab16 * 16 + L.table_bytes;
+        const size_t room = used < lds_budget ? std::min<size_t>(env_cap, lds_budget - used) : 0;
+        uint32_t count = 0;
+        while (count + 1 < e.n_levels && ((size_t) c->env_levels_total - e.level_offset[e.n_levels - 1 - count]) * 4 <= room) ++count;
+        if (count) {
+            L.cfg.env_top_count = count; L.cfg.env_top_base = e.level_offset[e.n_levels - count];
+            L.cfg.env_top_words = (uint32_t) (c->env_levels_total - L.cfg.env_top_base);
+            L.table_bytes += ((size_t) L.cfg.env_top_words + 3) / 4 * 16;
         }
-        // (only the kernels that call stage_tables ask for the table bytes: the phase machine and the packet kernels — `rlds`; the
-        // lock-step tree kernels, which read the tables from global memory, launch with `rlds_plain`: ADVICE r04)
-        L.rlds_plain = L.rlds;
-        if (L.tables_fit) L.rlds = (size_t) L.cfg.tab16 * 16 + L.table_bytes;
-        return L;
-    };
-    LdsLayout lay = lay_out(c->lds_bytes, 4096, lds_budget4);
-    // will this render walk the 8-wide tree? (the conditions mi_render applies below, known here already; MIW_BVH8=0 keeps the 4-wide walk)
-    const miw_pick::Facts facts = pick_facts(c, ropt);          // what the kernel-class rules read (kernel_pick.h)
-    const bool pre8 = plan == 2 && cfg->integrator != MI_INTEGRATOR_DIRECT && !c->lds_cfg.brute && c->lds_cfg.stack && tree8_on(c, ropt) &&
-                      !ropt.off("MIW_PHASED") && ropt.num("MIW_PHASED_WAVES", 4) == 4 && film_mode == 1;
-    bool stack8_sized = false;
+    }
+    // (only the kernels that call stage_tables ask for the table bytes: the phase machine and the packet kernels — `rlds`; the
+    // lock-step tree kernels, which read the tables from global memory, launch with `rlds_plain`: ADVICE r04)
+    L.rlds_plain = L.rlds;
+    if (L.tables_fit) L.rlds = (size_t) L.cfg.tab16 * 16 + L.table_bytes;
+    return L;
+}
+// the layouts a render may use: the default one — sized for the 8-wide tree's depth where the render may walk that tree (stack8_sized) — and the pooled kernel's
+struct RenderLds { LdsLayout lay, layp; bool walk8 = false, stack8_sized = false, pooled_fits = false; int pool_nw = 12, pool_pp = 1; };
+static mi_status render_lds(RenderFrame &F, const miw_pick::Facts &facts, RenderLds &L) {
+    mi_ctx *c = F.c; const Options &ropt = F.ropt; const bool rec16 = F.FP.rec16;
+    const size_t lds_budget4 = MIW_LDS_PER_WORKGROUP - MIW_LDS_STATIC - MIW_LDS_GRANULE;
+    LdsLayout &lay = L.lay;
+    lay = lds_layout(c, ropt, rec16, c->lds_bytes, 4096, lds_budget4);
+    // may this render walk the 8-wide tree? Everything the route asks for it (path_route: phased8) but that the tables fit the layout chosen here; MIW_BVH8=0 keeps the 4-wide walk
+    const bool pre8 = L.walk8 = F.plan == 2 && F.P.integrator != INTEG_DIRECT && !c->lds_cfg.brute && c->lds_cfg.stack && tree8_on(c, ropt) &&
+                                !ropt.off("MIW_PHASED") && ropt.num("MIW_PHASED_WAVES", 4) == 4 && F.FP.film_mode == 1;
+    bool &stack8_sized = L.stack8_sized;
     if (pre8 && !ropt.on("MIW_STACK8_FULL")) {
         const size_t base8 = (size_t) c->lds_cfg.stack16 * 16 + (size_t) std::max<uint32_t>(c->nodes8_depth, 2u) * MIW_BLOCK * sizeof(U2);
-        const LdsLayout lay8 = lay_out(base8, 12288, lds_budget4);
+        const LdsLayout lay8 = lds_layout(c, ropt, rec16, base8, 12288, lds_budget4);
         if (lay8.tables_fit && base8 <= c->lds_bytes) { lay = lay8; stack8_sized = true; }
     }
     // The pooled phase machine (device/pooled_kernel.h, round 6): ONE workgroup of MIW_POOL_NW wavefronts per CU whose lanes share their walks
     // through LDS — per lane an 8-byte stack entry per tree level + an 80-byte job record + a status byte, then thresholds, tables and the
     // environment warp's levels once per CU: [stacks][job records][status][thresholds][tables]. All of the CU's 160 KB may be one workgroup's.
     // MIW_POOLED=0 keeps k_path_phased (A/B runs, and what shards with placed queues run).
-    LdsLayout layp{}; bool pooled_fits = false;
+    LdsLayout &layp = L.layp; layp = LdsLayout{}; bool &pooled_fits = L.pooled_fits;
     // shape of the workgroup: NW wavefronts x PP pixels per lane — 12 x 1 (three wavefronts per SIMD), or 8 x 2 (two per SIMD, 256 VGPRs, twice the
     // jobs per lane: MIW_POOL_SHAPE=8x2; needs 1024 job records + stacks in LDS: trees of up to 8 levels)
-    int pool_nw = 12, pool_pp = 1;
+    int &pool_nw = L.pool_nw, &pool_pp = L.pool_pp;
     if (const char *e = ropt.get("MIW_POOL_SHAPE")) { int a = 0, b = 0; if (sscanf(e, "%dx%d", &a, &b) == 2 && ((a == 12 && b == 1) || (a == 8 && b == 2))) { pool_nw = a; pool_pp = b; } }
     // (the 8 x 2 shape is instantiated for the MATS_TRIO class only — BASELINE configs 3 / 4)
     if (!miw_pick::trio_kernel(facts)) { pool_nw = 12; pool_pp = 1; }
@@ -2096,477 +2127,571 @@ mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
         size_t base = (size_t) std::max<uint32_t>(c->nodes8_depth, 2u) * NJ * sizeof(U2);
         const uint32_t pool16 = (uint32_t) (base / 16); base += 5u * NJ * 16u;
         const uint32_t stat16 = (uint32_t) (base / 16); base += NJ;
-        layp = lay_out(base, 32768, (size_t) 160u * 1024u - 1024u);
+        layp = lds_layout(c, ropt, rec16, base, 32768, (size_t) 160u * 1024u - 1024u);
         layp.cfg.stack16 = 0u; layp.cfg.pool16 = pool16; layp.cfg.stat16 = stat16; layp.cfg.nodes_staged = layp.cfg.tris_staged = 0u;
         pooled_fits = layp.tables_fit;
         if (ropt.get("MIW_DEBUG")) fprintf(stderr, "[miwave] pooled phase machine: %d wavefronts per workgroup x %d pixels per lane, LDS %zu bytes (stacks %zu, job records %zu, tables %zu of which environment warp levels %u), fits %d\n",
                                          pool_nw, pool_pp, layp.rlds, (size_t) pool16 * 16, 5u * NJ * 16u, layp.table_bytes, layp.cfg.env_top_words * 4u, (int) pooled_fits);
     }
-    TraceLds rcfg = lay.cfg; size_t rlds = lay.rlds; const size_t rlds_plain = lay.rlds_plain, table_bytes = lay.table_bytes; const bool tables_fit = lay.tables_fit;
+    const TraceLds &rcfg = lay.cfg; const size_t rlds = lay.rlds, rlds_plain = lay.rlds_plain, table_bytes = lay.table_bytes; const bool tables_fit = lay.tables_fit;
     if (MIW_LDS_TABLES && c->lds_cfg.brute && !tables_fit) return fail(c, MI_ERR_STATE, "render: the tables of this packet scene do not fit a workgroup's LDS");
-    // workgroups of a kernel with `dyn` bytes of dynamic LDS (+ its static __shared__, in granules) that one CU holds
-    auto lds_workgroups = [](size_t dyn) -> uint32_t {
-        const size_t per = (dyn + MIW_LDS_STATIC + 16u + MIW_LDS_GRANULE - 1u) / MIW_LDS_GRANULE * MIW_LDS_GRANULE;
-        return (uint32_t) (MIW_LDS_PER_CU / per);
-    };
     if (ropt.get("MIW_DEBUG")) fprintf(stderr, "[miwave] LDS per workgroup: %zu bytes dynamic with the scene tables (%zu without), tables %zu B of which environment warp levels %u B and built frame tables %u B, budget %zu%s; + %u static: %u workgroups per CU by LDS\n",
                                      rlds, rlds_plain, table_bytes, rcfg.env_top_words * 4u, (rcfg.tab_words[10] + rcfg.tab_words[11]) * 4u, lds_budget4, stack8_sized ? "; stack sized for the 8-wide tree's depth" : "",
-                                     MIW_LDS_STATIC + 16u, lds_workgroups(rlds));
+                                     MIW_LDS_STATIC + 16u, miw_plan::lds_workgroups(rlds));
+    return MI_OK;
+}
 
-    mi_counters &K = c->counters;
-    K.samples = K.segments = K.shadow_rays = K.iterations = 0; K.lanes = n_lanes;
+// ---- mi_render: the counters of the render that begins; what a device counter shard holds summed into them; the job's time limit ----
+static void counters_reset(RenderFrame &F) {
+    mi_ctx *c = F.c; mi_counters &K = F.K;
+    K.samples = K.segments = K.shadow_rays = K.iterations = 0; K.lanes = F.n_lanes;
     K.ms_trace_closest = K.ms_trace_any = K.ms_shade = K.ms_init = K.ms_resolve = K.ms_path = K.ms_film_blocks = K.ms_film_merge = K.ms_film_pack = 0;
     K.n_trace_closest = K.n_trace_any = K.n_shade = K.n_path = 0; K.path_kernel = 0; K.placed = 0; K.tree_width = 0; K.pooled = 0; K.pool_waves = 0; K.film_overlapped = 0; K.film_groups = 0; K.job_chunk = 0; K.job_chunks = 0; c->replay_enqueued = false; K.place_cost_max = K.place_cost_unit = K.place_max_pixel = K.place_measure_spp = 0; K.place_cost_mean = 0.0;
 
-    LaunchTimer T{ c, K, cfg->profile != 0 };                    // HIP-event time per launch class (mi_counters::ms_*)
-#define MIW_TIMED(cls_, launch) do {                                                   \
-        size_t e0_ = 0, e1_ = 0;                                                       \
-        if (T.on) { HIP_TRY(c, T.get_event(e0_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e0_], s)); } \
-        launch;                                                                        \
-        if (T.on) { HIP_TRY(c, T.get_event(e1_)); HIP_TRY(c, hipEventRecord(c->ev_pool[e1_], s)); \
-                    T.stamps.push_back({ cls_, e0_, e1_ }); }                          \
-    } while (0)
+}
+static mi_status read_counters(RenderFrame &F, Counters &sum) {
+    mi_ctx *c = F.c; hipStream_t s = F.s; mi_counters &K = F.K;
+    HIP_TRY(c, hipMemcpyAsync(c->h_cnt, c->d_cnt.p, sizeof(Counters) * MIW_CNT_SHARDS, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    sum.segments = sum.samples = sum.shadow_rays = sum.active_lanes = 0;
+    for (int i = 0; i < MIW_CNT_SHARDS; ++i) {
+        sum.segments += c->h_cnt[i].segments; sum.samples += c->h_cnt[i].samples;
+        sum.shadow_rays += c->h_cnt[i].shadow_rays; sum.active_lanes += c->h_cnt[i].active_lanes;
+    }
+    K.samples = sum.samples; K.segments = sum.segments; K.shadow_rays = sum.shadow_rays;
+    return MI_OK;
+}
+static bool out_of_time(const RenderFrame &F) {
+    return F.cfg->timeout_s > 0.f &&
+           std::chrono::duration<double>(std::chrono::steady_clock::now() - F.wall0).count() > F.cfg->timeout_s;
+}
+// the context's view with the 8-wide tree's nodes, and the triangles / vertex normals in that tree's order (hit records of its walks name triangles in it)
+static SceneView view_over_tree8(const mi_ctx *c) {
+    SceneView v = c->view;
+    v.nodes8 = c->d_nodes8.p; v.tris = c->d_tris8.p; if (v.tri_vn) v.tri_vn = c->d_tri_vn8.p;
+    return v;
+}
+// what k_init_pixels / k_init_lanes read of the frame's geometry
+static InitArgs init_args(const RenderFrame &F) {
+    InitArgs A; A.block_ids = F.c->d_block_ids.p; A.tile_list = F.cfg->tile_list ? F.c->d_tile_list.p : nullptr;
+    A.blocks_x = F.blocks_x; A.blocks_y = F.blocks_y; A.bs = F.bs; A.bs2_log2 = F.bs2_log2; A.base_seed = F.cfg->base_seed;
+    return A;
+}
 
-    mi_status result = MI_OK;
-    auto read_counters = [&](Counters &sum) -> mi_status {
-        HIP_TRY(c, hipMemcpyAsync(c->h_cnt, c->d_cnt.p, sizeof(Counters) * MIW_CNT_SHARDS, hipMemcpyDeviceToHost, s));
+// ---- mi_render, resident plan, phase "route": which path kernel runs and how its pixels reach it — every flag decided once, before the first launch ----
+struct PathRoute {
+    bool direct, tiny;
+    uint32_t n_simd, per_launch;                                  // placed queues: one per SIMD; samples per launch
+    bool phased, phased_placeable, phased8; int ph_waves;         // the phase machine; its Placed instantiations; over the 8-wide tree; its wavefronts per SIMD
+    bool packet_shard4; uint32_t feat, res_waves;                 // the four-wavefront shard kernel; the scene-feature mask; wavefronts per SIMD that ARE resident
+    bool place; uint32_t measure_end, n_pieces;                   // measuring + placed launch; the measuring launch's samples; 64-lane pieces
+    int overlap_mode; bool overlap;                               // the film replay beside the render (MIW_FILM_OVERLAP)
+    bool pooled;                                                  // k_path_pooled
+};
+static mi_status path_route(RenderFrame &F, const miw_pick::Facts &facts, const RenderLds &L, PathRoute &R) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; const FilmPlan &FP = F.FP;
+    const int film_mode = FP.film_mode; const uint32_t n_lanes = F.n_lanes, n_tiles = F.n_tiles;
+    const bool direct = F.P.integrator == INTEG_DIRECT, tables_fit = L.lay.tables_fit; const size_t rlds = L.lay.rlds;
+    const uint32_t n_simd = (uint32_t) c->cu_count * 4u;                                  // placed queues: one per SIMD
+    const uint32_t per_launch = cfg->samples_per_launch > 0 ? (uint32_t) cfg->samples_per_launch : 128u;
+    // Shards of at most one pixel per resident lane (an N-GPU frame at N >= 8): a short measuring launch (the first eighth of the
+    // samples, at least 16) records what every 64-lane piece costs, the pieces are dealt to the SIMDs longest-first, and the
+    // rest of the samples run with every wavefront taking its pixels from the queue of the SIMD it sits on (resident_kernel.h:
+    // QueueWork). Same samples, same log slots: the film does not change. MIW_PLACE = 0 | 1 overrides.
+    // (packet kernels only — QueueWork<Placed> — and only where every pixel of the shard can be resident at once: 4 wavefronts per SIMD
+    // for the plain-diffuse packet kernel, 3 for the others — a shard larger than that is balanced by the queue itself)
+    // Which path kernel runs (decided here because placement depends on it): tree scenes with the LDS-stack walk get the wave-level
+    // phase machine (device/phased_kernel.h; MIW_PHASED=0 keeps the lock-step kernel, MIW_TRIO=0 the full BSDF table: A/B runs)
+    const bool tiny = facts.tiny;
+    const bool phased_on = !ropt.off("MIW_PHASED");
+    const bool trio_kernel = miw_pick::trio_kernel(facts);
+    const bool phased = phased_on && !direct && !tiny && c->lds_cfg.stack && (c->view.nodes4 != nullptr || trio_kernel) && (tables_fit || !MIW_LDS_TABLES);
+    // 4 waves per SIMD for every tree (measured: 0.9 M triangles +7 - 11 %, 41 k triangles +-0 before the register diet, +8 % after); MIW_PHASED_WAVES = 3 | 4 overrides
+    const int ph_waves = ropt.num("MIW_PHASED_WAVES", 4) == 4 ? 4 : 3;
+    const bool phased_placeable = phased && c->view.nodes4 != nullptr && ph_waves == 4;     // (the Placed instantiations: the 4-wide tree at four waves per SIMD)
+    // the 8-wide tree whenever mi_bvh_build produced one (four waves per SIMD only; MIW_BVH8=0 here keeps the 4-wide walk: A/B runs in one process)
+    // (render_lds asked everything else of this — walk8 — before it chose the layout whose tables_fit `phased` reads)
+    const bool phased8 = phased_placeable && L.walk8;
+    if (L.stack8_sized && !phased8) return fail(c, MI_ERR_STATE, "render: the LDS stack was sized for the 8-wide walk, which this launch does not run");
+    // wavefronts per SIMD of the path kernel this render launches (resident_kernel.h / phased_kernel.h / trace.h: what each is compiled for)
+    // (the plain-diffuse packet kernel of <= 32 triangles: five — or, when the job's pixels fill no more than four wavefronts per SIMD (a rank's shard), the
+    // 128-register instantiation for four: resident_kernel.h; MIW_PACKET_SHARD4=0 keeps five)
+    bool packet_shard4 = !phased && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct && c->view.tri_count <= 32u && MIW_PACKET_WAVES > 4 && film_mode == 1 && n_lanes <= 64u * 4u * n_simd;
+    if (ropt.off("MIW_PACKET_SHARD4")) packet_shard4 = false;
+    // the scene features compiled into the packet path kernel (miw/scene.h: FEAT_*): facts of the uploaded scene and of this render; MIW_LEAN=0 keeps them all
+    const uint32_t feat = miw_pick::packet_features_kernel(miw_pick::packet_features(c->have_env, c->shape_normals, c->emitter_normals, cfg->moment_pass != 0), !ropt.off("MIW_LEAN"));
+    const uint32_t res_waves_compiled = miw_plan::res_waves_compiled(phased, (uint32_t) ph_waves, tiny, c->diffuse_only && !MIW_SPECTRAL, c->view.tri_count <= 32u, packet_shard4,
+                                                                     (uint32_t) MIW_TREE_WAVES, (uint32_t) MIW_PACKET_WAVES, (uint32_t) MIW_PACKET_WAVES_ALL);
+    // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
+    // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
+    const uint32_t res_waves = tiny && film_mode == 1 ? std::max(1u, std::min(res_waves_compiled, miw_plan::lds_workgroups(rlds))) : res_waves_compiled;
+    bool place = film_mode == 1 && !direct && (tiny || phased_placeable) && miw_plan::place_window(n_lanes, res_waves, n_simd) &&
+                 cfg->spp >= 128u && per_launch >= cfg->spp && cfg->timeout_s <= 0.f;
+    if (ropt.off("MIW_PLACE")) place = false;
+    uint32_t measure_div = (uint32_t) std::max(2, ropt.num("MIW_PLACE_MEASURE", 8));                                 // the measuring launch runs spp / 8 samples (MIW_PLACE_MEASURE = divisor)
+    const uint32_t measure_end = place ? std::max<uint32_t>(16u, cfg->spp / measure_div) : 0u;
+    const uint32_t n_pieces = (n_lanes + 63u) / 64u;
+    // the film replay beside the render (overlap_prepare / overlap_enqueue above): frames replayed by k_film_lanes over the tile-interleaved log whose
+    // samples all run in ONE launch (a pixel is complete when that launch stores it), no placement, no time limit
+    // OPT-IN (MIW_FILM_OVERLAP=1): measured at C2 (gpurun r6k - r6m, profiles/r06_experiments.txt) it hides up to 3/4 of the replay and gains 0 - 1 % of the
+    // frame — the wave slots it needs cost the path kernel in proportion (32 workgroups short: +6 ms), a replay wavefront beside three packet-kernel
+    // wavefronts takes 20 - 30 ms instead of 5, and what is left after the path kernel cannot take less than one wavefront's chain (~8 - 10 ms)
+    const int overlap_mode = ropt.num("MIW_FILM_OVERLAP", 0);
+    const bool overlap = overlap_mode != 0 && c->overlap_state != 0 && film_mode == 1 && FP.rec16 && FP.film_lanes != 0 && FP.log_il != 0 && !place && !phased /* (QueueWork<..., Groups = false>) */ && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct /* the 120-register packet kernel: the only one a replay wavefront fits beside */ &&
+                         per_launch >= cfg->spp && cfg->timeout_s <= 0.f && n_tiles > 0;
+#if MIW_SPECTRAL
+    const bool pooled = false;
+#else
+    const bool pooled = phased8 && !place && L.pooled_fits;
+#endif
+    R.direct = direct; R.tiny = tiny; R.n_simd = n_simd; R.per_launch = per_launch;
+    R.phased = phased; R.phased_placeable = phased_placeable; R.phased8 = phased8; R.ph_waves = ph_waves;
+    R.packet_shard4 = packet_shard4; R.feat = feat; R.res_waves = res_waves;
+    R.place = place; R.measure_end = measure_end; R.n_pieces = n_pieces;
+    R.overlap_mode = overlap_mode; R.overlap = overlap; R.pooled = pooled;
+    return MI_OK;
+}
+
+// ---- mi_render, resident plan, phase "placement" (shards of at most one pixel per resident lane: path_route's `place`) ----
+// place_prepare, before the measuring launch: the cost, sort and queue buffers, cleared
+static mi_status place_prepare(RenderFrame &F, const PathRoute &R, size_t &place_tmp_bytes) {
+    mi_ctx *c = F.c; hipStream_t s = F.s; const uint32_t n_lanes = F.n_lanes, n_pieces = R.n_pieces, n_simd = R.n_simd;
+    HIP_TRY(c, c->d_lane_cost.resize(n_lanes)); HIP_TRY(c, c->d_cost_sorted.resize(n_lanes)); HIP_TRY(c, c->d_lane_iota.resize(n_lanes));
+    HIP_TRY(c, c->d_lane_sorted.resize((size_t) n_pieces * 64u));
+    HIP_TRY(c, c->d_piece_list.resize((size_t) n_simd * MIW_PLACE_PIECES)); HIP_TRY(c, c->d_simd_ids.resize(1u + (1u << 14)));
+    HIP_TRY(c, hipMemsetAsync(c->d_lane_cost.p, 0, n_lanes * sizeof(uint32_t), s));      // (lanes without a pixel never report: cost 0, sorted last)
+    HIP_TRY(c, hipMemsetAsync(c->d_lane_sorted.p, 0xff, (size_t) n_pieces * 64u * sizeof(uint32_t), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_simd_ids.p, 0, c->d_simd_ids.n * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_iota, dim3((n_lanes + 255u) / 256u), dim3(256), 0, s, c->d_lane_iota.p, n_lanes);
+    HIP_TRY(c, rocprim::radix_sort_pairs_desc(nullptr, place_tmp_bytes, c->d_lane_cost.p, c->d_cost_sorted.p, c->d_lane_iota.p, c->d_lane_sorted.p, (size_t) n_lanes, 0u, 32u, s));
+    HIP_TRY(c, c->d_place_tmp.resize(place_tmp_bytes + 16));
+    return MI_OK;
+}
+// place_deal, between the measuring launch and the placed one: sort the lanes by cost, read the SIMD registry, deal the pieces to the queues, upload
+static mi_status place_deal(RenderFrame &F, const PathRoute &R, size_t place_tmp_bytes, TraceLds &rcfg, bool &place_stats_due) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; hipStream_t s = F.s; LaneQueues &Q = F.Q; mi_counters &K = F.K;
+    const uint32_t n_lanes = F.n_lanes, n_pieces = R.n_pieces; const bool phased = R.phased, phased8 = R.phased8;
+    // the lanes by what their pixel cost, dearest first (device radix sort), cut into pieces of 64: consecutive sorted lanes
+    // (the pixels of a wavefront cost about the same and finish together), or every pieces-th one (one pixel of every cost
+    // stratum per wavefront). Either way a piece's cost is that of its first (dearest) lane.
+    HIP_TRY(c, rocprim::radix_sort_pairs_desc(c->d_place_tmp.p, place_tmp_bytes, c->d_lane_cost.p, c->d_cost_sorted.p, c->d_lane_iota.p, c->d_lane_sorted.p, (size_t) n_lanes, 0u, 32u, s));
+    // Which cut: measured on rank 0's 1/8 shard (gpurun r4b, path kernel ms at 256 / 128 / 512 spp; no placement -> consecutive
+    // -> spread): material balls 99.3 -> 90.7 -> 104.9, 0.9 M-triangle interior 130.8 -> 131.0 -> 120.9, Cornell packets
+    // 40.0 -> 36.7 -> 44.3. Consecutive pieces keep the dear pixels in few wavefronts, which the priorities then favour; the
+    // interior — every pixel dear, its walks bound by memory latency, tree and triangles beyond the L2s — gains from every
+    // wavefront carrying the same mix. Rule: spread when the tree does not fit the aggregate L2 (32 MB). MIW_PLACE_SPREAD = 0 | 1 overrides.
+    bool spread = phased && ((phased8 ? (size_t) c->nodes8_count * sizeof(Bvh8Node) : (size_t) c->nodes4_count * sizeof(Bvh4Node)) + (size_t) c->view.tri_count * sizeof(Tri)) > ((size_t) 32 << 20);
+    if (const char *e = ropt.get("MIW_PLACE_SPREAD")) spread = atoi(e) != 0;
+    Q.piece_a = spread ? 1u : 64u; Q.piece_b = spread ? n_pieces : 1u;
+    // one host round trip between the measuring launch and the placed one, and only for the SIMD registry: the pieces' costs stay on the
+    // device (the dealing below needs their ORDER only, which the sort fixed; round 6 — the statistics of the measuring launch,
+    // mi_counters::place_*, are read after the frame's last launch, below)
+    // the SIMDs the measuring launch ran on, numbered 0 .. nqueues - 1 (simd_ids[1 + hardware key]; word 0 = the "all dry" flag)
+    std::vector<uint32_t> &ids = c->h_simd_ids;
+    ids.resize(c->d_simd_ids.n);
+    HIP_TRY(c, hipMemcpyAsync(ids.data(), c->d_simd_ids.p, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    place_stats_due = cfg->profile != 0;
+    uint32_t nqueues = 0;
+    for (size_t k = 1; k < ids.size(); ++k) ids[k] = ids[k] ? nqueues++ : 0xffffffffu;
+    ids[0] = 0u;
+    // the pieces dealt to the queues in alternating rounds (render_plan.h: deal_pieces); fewer than two SIMDs, or more pieces than slots: one queue (cannot happen on a whole device)
+    std::vector<uint32_t> &list = c->h_piece_list;                                          // (context-owned: the upload below is not waited for)
+    nqueues = miw_plan::deal_pieces(n_pieces, nqueues, MIW_PLACE_PIECES, list);
+    if (nqueues) {
+        HIP_TRY(c, c->d_piece_list.resize(list.size()));
+        HIP_TRY(c, hipMemcpyAsync(c->d_piece_list.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_simd_ids.p, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        rcfg.queues = nqueues; Q.piece_list = c->d_piece_list.p; Q.lane_sorted = c->d_lane_sorted.p; Q.simd_ids = c->d_simd_ids.p;
+        K.placed = 1u;
+    }
+    return MI_OK;
+}
+// place_statistics, after the frame's last launch: what the measuring launch found (profile runs) and how the placed launch went (MIW_DEBUG)
+static mi_status place_statistics(RenderFrame &F, const PathRoute &R, bool place_stats_due) {
+    mi_ctx *c = F.c; const Options &ropt = F.ropt; hipStream_t s = F.s; const LaneQueues &Q = F.Q; mi_counters &K = F.K;
+    const uint32_t n_lanes = F.n_lanes, n_pieces = R.n_pieces, n_simd = R.n_simd, measure_end = R.measure_end; const bool phased = R.phased;
+    if (place_stats_due) {             // what the measuring launch found (mi_counters::place_*): the shard's dearest pixel and the mean
+        std::vector<uint32_t> all(n_lanes); uint32_t first_lane = 0, px = 0;
+        HIP_TRY(c, hipMemcpyAsync(all.data(), c->d_cost_sorted.p, (size_t) n_lanes * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&first_lane, c->d_lane_sorted.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        sum.segments = sum.samples = sum.shadow_rays = sum.active_lanes = 0;
-        for (int i = 0; i < MIW_CNT_SHARDS; ++i) {
-            sum.segments += c->h_cnt[i].segments; sum.samples += c->h_cnt[i].samples;
-            sum.shadow_rays += c->h_cnt[i].shadow_rays; sum.active_lanes += c->h_cnt[i].active_lanes;
+        if (first_lane < n_lanes) HIP_TRY(c, hipMemcpy(&px, c->q_pixel.p + first_lane, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        double csum = 0.0; uint32_t with = 0;
+        for (uint32_t v : all) if (v) { csum += (double) v; ++with; }
+        K.place_cost_max = all.empty() ? 0u : all[0]; K.place_cost_mean = with ? csum / with : 0.0; K.place_max_pixel = px;
+        K.place_cost_unit = phased ? 1u : 0u; K.place_measure_spp = measure_end;
+    }
+    if (K.placed && ropt.get("MIW_DEBUG")) {                     // how the placed launch went: SIMDs that registered, lanes handed out per queue
+        std::vector<uint32_t> cur(n_simd), ids(1u + (1u << 14)), cost(n_pieces);
+        (void) hipMemcpy(cur.data(), c->d_next_pixel.p, n_simd * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        (void) hipMemcpy(ids.data(), c->d_simd_ids.p, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        (void) hipMemcpy2D(cost.data(), sizeof(uint32_t), c->d_cost_sorted.p, Q.piece_a * sizeof(uint32_t), sizeof(uint32_t), n_pieces, hipMemcpyDeviceToHost);
+        uint32_t keys = 0, key_or = 0, full = 0, over = 0; uint64_t csum = 0; uint32_t cmin = ~0u, cmax = 0;
+        for (uint32_t k = 0; k < (1u << 14); ++k) if (ids[1 + k] != 0xffffffffu) { ++keys; key_or |= k; }
+        ids[0] = keys;
+        for (uint32_t v : cur) { full += v >= 64u * MIW_PLACE_PIECES; over += v > 64u * MIW_PLACE_PIECES; }
+        for (uint32_t v : cost) { csum += v; cmin = std::min(cmin, v); cmax = std::max(cmax, v); }
+        fprintf(stderr, "[miwave] placed queues: %u SIMDs numbered, %u distinct hardware keys (bits used 0x%x), %u of %u queues drained (%u asked beyond their end), "
+                        "cost of the dearest pixel of a piece min / mean / max = %u / %.0f / %u (iterations, or 256-cycle units)\n", ids[0], keys, key_or, full, n_simd, over, cmin, (double) csum / n_pieces, cmax);
+    }
+    return MI_OK;
+}
+
+// ---- mi_render, resident plan, phase "chunk jobs": LaneQueues::job_* and mi_counters::job_chunk* of the launch that begins at sample `done` ----
+static void chunk_jobs(RenderFrame &F, const PathRoute &R, const RenderLds &L, uint32_t done) {
+    const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; LaneQueues &Q = F.Q; mi_counters &K = F.K; const uint32_t n_lanes = F.n_lanes;
+    const bool tiny = R.tiny, phased = R.phased, place = R.place, overlap = R.overlap, pooled_fits = L.pooled_fits;
+    const uint32_t per_launch = R.per_launch, res_waves = R.res_waves, n_simd = R.n_simd;
+    // chunk jobs (resident_kernel.h: QueueWork::fetch): full frames of the packet kernels, all samples in one launch. Without them a frame of N pixels
+    // on L resident lanes lasts ceil(N / L) rounds of one PIXEL (every lane starts at once, a pixel's samples are one serial job, the jobs are about
+    // equally long): C2 = 6.33 -> 7; with chunks of spp / 8 samples ceil(8 N / L) / 8 = 6.375.
+    Q.job_chunk = Q.job_pow = Q.job_total = 0u; Q.job_min = 0x80000000u;
+    // Every job costs one atomic on ONE address (the queue's counter) and a hand-over (a 16-byte state word out and in, past the L2): uniform chunks of
+    // 8 / 16 / 32 samples ran C2 in 702 / 496 / 305 ms, 64 / 128 / 256 in 226.8 / 226.5 / 230.6, whole pixels in 239.3 (gpurun r6p). So the chunks
+    // HALVE — a chunk ends where the samples still to do are a power of two — down to job_min samples (512 spp: 256 + 128 + 64 + 64): four hand-overs
+    // per pixel instead of eight, the tail as long as the smallest. The phase machine's full frames (C3, C4) take the same queue.
+    if ((tiny || (phased && MIW_PHASED_JOBS != 0)) && !pooled_fits && !place && !overlap && done == 0 && per_launch >= cfg->spp && cfg->timeout_s <= 0.f) {
+        uint32_t jmin = tiny ? 64u : 32u;                                 // (gpurun r6s, halving chunks: C2 4 461 / 4 316 / 4 389 Msamples/s at 64 / 32 / 128; C3 1 298 / 1 305, C4 522 / 528 at 64 / 32)
+        if (const char *e = ropt.get("MIW_JOB_CHUNK")) jmin = (uint32_t) std::max(0, atoi(e));   // (a value that is no power of two: off — render_plan.h: chunk_schedule)
+        // from 1.2 pixels per resident lane on (render_plan.h: chunks_enough)
+        bool enough = miw_plan::chunks_enough(n_lanes, res_waves, n_simd);
+        if (ropt.on("MIW_JOB_CHUNK_FORCE")) enough = true;
+        const miw_plan::ChunkSchedule cs = miw_plan::chunk_schedule(cfg->spp, jmin);
+        if (cs.job_min && enough && cs.chunks >= 2u && (uint64_t) n_lanes * cs.chunks < (1ull << 31)) {
+            Q.job_chunk = cs.job_min; Q.job_min = cs.job_min; Q.job_pow = cs.job_pow; Q.job_total = (uint32_t) ((uint64_t) n_lanes * cs.chunks);
+            K.job_chunk = cs.job_min; K.job_chunks = (uint32_t) cs.chunks;
         }
-        K.samples = sum.samples; K.segments = sum.segments; K.shadow_rays = sum.shadow_rays;
-        return MI_OK;
-    };
-    auto out_of_time = [&]() {
-        return cfg->timeout_s > 0.f &&
-               std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > cfg->timeout_s;
-    };
-    if (n_lanes > 0 && plan == 2) {
-        // ---- resident plan: every pixel advances `per_launch` samples per launch ----
-        dim3 grid((n_lanes + MIW_BLOCK - 1) / MIW_BLOCK), block(MIW_BLOCK);
-        InitArgs A; A.block_ids = c->d_block_ids.p; A.tile_list = cfg->tile_list ? c->d_tile_list.p : nullptr;
-        A.blocks_x = blocks_x; A.blocks_y = blocks_y; A.bs = bs; A.bs2_log2 = bs2_log2; A.base_seed = cfg->base_seed;
-        MIW_TIMED(3, hipLaunchKernelGGL(k_init_pixels, grid, block, 0, s, P, c->q_st.p, c->q_pixel.p, A));
-        HIP_TRY(c, hipGetLastError());
-        const uint32_t n_simd = (uint32_t) c->cu_count * 4u;                                  // placed queues: one per SIMD
-        HIP_TRY(c, c->d_next_pixel.resize(std::max<uint32_t>(8u, n_simd)));
-        const uint32_t per_launch = cfg->samples_per_launch > 0 ? (uint32_t) cfg->samples_per_launch : 128u;
-        // Shards of at most one pixel per resident lane (an N-GPU frame at N >= 8): a short measuring launch (the first eighth of the
-        // samples, at least 16) records what every 64-lane piece costs, the pieces are dealt to the SIMDs longest-first, and the
-        // rest of the samples run with every wavefront taking its pixels from the queue of the SIMD it sits on (resident_kernel.h:
-        // QueueWork). Same samples, same log slots: the film does not change. MIW_PLACE = 0 | 1 overrides.
-        // (packet kernels only — QueueWork<Placed> — and only where every pixel of the shard can be resident at once: 4 wavefronts per SIMD
-        // for the plain-diffuse packet kernel, 3 for the others — a shard larger than that is balanced by the queue itself)
-        // Which path kernel runs (decided here because placement depends on it): tree scenes with the LDS-stack walk get the wave-level
-        // phase machine (device/phased_kernel.h; MIW_PHASED=0 keeps the lock-step kernel, MIW_TRIO=0 the full BSDF table: A/B runs)
-        const bool tiny = facts.tiny;
-        const bool phased_on = !ropt.off("MIW_PHASED");
-        const bool trio_kernel = miw_pick::trio_kernel(facts);
-        const bool phased = phased_on && !direct && !tiny && c->lds_cfg.stack && (c->view.nodes4 != nullptr || trio_kernel) && (tables_fit || !MIW_LDS_TABLES);
-        // 4 waves per SIMD for every tree (measured: 0.9 M triangles +7 - 11 %, 41 k triangles +-0 before the register diet, +8 % after); MIW_PHASED_WAVES = 3 | 4 overrides
-        const int ph_waves = ropt.num("MIW_PHASED_WAVES", 4) == 4 ? 4 : 3;
-        const bool phased_placeable = phased && c->view.nodes4 != nullptr && ph_waves == 4;     // (the Placed instantiations: the 4-wide tree at four waves per SIMD)
-        // the 8-wide tree whenever mi_bvh_build produced one (four waves per SIMD only; MIW_BVH8=0 here keeps the 4-wide walk: A/B runs in one process)
-        const bool phased8 = phased_placeable && tree8_on(c, ropt);
-        if (stack8_sized && !phased8) return fail(c, MI_ERR_STATE, "render: the LDS stack was sized for the 8-wide walk, which this launch does not run");
-        SceneView view8 = c->view;
-        if (phased8) { view8.nodes8 = c->d_nodes8.p; view8.tris = c->d_tris8.p; if (view8.tri_vn) view8.tri_vn = c->d_tri_vn8.p; }
-        // wavefronts per SIMD of the path kernel this render launches (resident_kernel.h / phased_kernel.h / trace.h: what each is compiled for)
-        // (the plain-diffuse packet kernel of <= 32 triangles: five — or, when the job's pixels fill no more than four wavefronts per SIMD (a rank's shard), the
-        // 128-register instantiation for four: resident_kernel.h; MIW_PACKET_SHARD4=0 keeps five)
-        bool packet_shard4 = !phased && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct && c->view.tri_count <= 32u && MIW_PACKET_WAVES > 4 && film_mode == 1 && n_lanes <= 64u * 4u * n_simd;
-        if (ropt.off("MIW_PACKET_SHARD4")) packet_shard4 = false;
-        // the scene features compiled into the packet path kernel (miw/scene.h: FEAT_*): facts of the uploaded scene and of this render; MIW_LEAN=0 keeps them all
-        const uint32_t feat = miw_pick::packet_features_kernel(miw_pick::packet_features(c->have_env, c->shape_normals, c->emitter_normals, cfg->moment_pass != 0), !ropt.off("MIW_LEAN"));
-        const uint32_t res_waves_compiled = phased ? (uint32_t) ph_waves : !tiny ? (uint32_t) MIW_TREE_WAVES : (c->diffuse_only && !MIW_SPECTRAL ? (c->view.tri_count <= 32u && !packet_shard4 ? (uint32_t) MIW_PACKET_WAVES : 4u) : (uint32_t) MIW_PACKET_WAVES_ALL);
-        // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
-        // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
-        const uint32_t res_waves = tiny && film_mode == 1 ? std::max(1u, std::min(res_waves_compiled, lds_workgroups(rlds))) : res_waves_compiled;
-        bool place = film_mode == 1 && !direct && (tiny || phased_placeable) && n_lanes >= 64u * n_simd / 2u && n_lanes <= 64u * res_waves * n_simd &&
-                     cfg->spp >= 128u && per_launch >= cfg->spp && cfg->timeout_s <= 0.f;
-        if (ropt.off("MIW_PLACE")) place = false;
-        uint32_t measure_div = (uint32_t) std::max(2, ropt.num("MIW_PLACE_MEASURE", 8));                                 // the measuring launch runs spp / 8 samples (MIW_PLACE_MEASURE = divisor)
-        const uint32_t measure_end = place ? std::max<uint32_t>(16u, cfg->spp / measure_div) : 0u;
-        const uint32_t n_pieces = (n_lanes + 63u) / 64u;
-        size_t place_tmp_bytes = 0;
-        if (place) {
-            HIP_TRY(c, c->d_lane_cost.resize(n_lanes)); HIP_TRY(c, c->d_cost_sorted.resize(n_lanes)); HIP_TRY(c, c->d_lane_iota.resize(n_lanes));
-            HIP_TRY(c, c->d_lane_sorted.resize((size_t) n_pieces * 64u));
-            HIP_TRY(c, c->d_piece_list.resize((size_t) n_simd * MIW_PLACE_PIECES)); HIP_TRY(c, c->d_simd_ids.resize(1u + (1u << 14)));
-            HIP_TRY(c, hipMemsetAsync(c->d_lane_cost.p, 0, n_lanes * sizeof(uint32_t), s));      // (lanes without a pixel never report: cost 0, sorted last)
-            HIP_TRY(c, hipMemsetAsync(c->d_lane_sorted.p, 0xff, (size_t) n_pieces * 64u * sizeof(uint32_t), s));
-            HIP_TRY(c, hipMemsetAsync(c->d_simd_ids.p, 0, c->d_simd_ids.n * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_iota, dim3((n_lanes + 255u) / 256u), dim3(256), 0, s, c->d_lane_iota.p, n_lanes);
-            HIP_TRY(c, rocprim::radix_sort_pairs_desc(nullptr, place_tmp_bytes, c->d_lane_cost.p, c->d_cost_sorted.p, c->d_lane_iota.p, c->d_lane_sorted.p, (size_t) n_lanes, 0u, 32u, s));
-            HIP_TRY(c, c->d_place_tmp.resize(place_tmp_bytes + 16));
-        }
-        // film_mode 2: workgroup-local float64 tile in LDS (needs 16x16-pixel workgroups: block_size >= 16)
-        TileArgs TA; memset(&TA, 0, sizeof TA);
-        size_t tile_bytes = 0;
-        if (film_mode == 2 && bs >= 16) {
-            TA.tile_list = A.tile_list; TA.blocks_x = blocks_x; TA.bs = bs; TA.bs2_log2 = bs2_log2;
-            TA.side = 16u + 2u * std::max<uint32_t>((uint32_t) cfg->filter_border, (uint32_t) floorf(cfg->filter_radius + .5f));
-            TA.geom16 = (uint32_t) ((c->lds_bytes + 15) / 16);
-            tile_bytes = (size_t) TA.geom16 * 16 - c->lds_bytes + (size_t) TA.side * TA.side * MIW_FILM_CHANNELS * sizeof(double);
-            if (c->lds_bytes + tile_bytes > 64 * 1024) {
+    }
+}
+
+// ---- mi_render, resident plan, phase "launch": one launch of the path kernel up to sample `end` — the dispatch over every kernel class, with the
+// launch's constants (rcfg / ph_cfg / pcfg) and grid ----
+struct PathLaunch {
+    dim3 grid;                                                    // one workgroup per MIW_BLOCK lanes: the persistent grids are cut from it
+    TraceLds rcfg;                                                // the render's layout; queues: 1, or the SIMD count for the placed launch (place_deal)
+    SceneView view8;                                              // the context's view over the 8-wide tree's nodes and triangle order (path_route: phased8)
+    TileArgs TA; size_t tile_bytes = 0;                           // film_mode 2: the workgroup-local float64 tile (atomic_film_tile)
+    uint32_t end = 0;
+    uint32_t feat_launched = FEAT_ALL;                            // the mask of the instantiation this launch IS: set where a lean twin is launched (MIW_DEBUG prints it)
+    bool frame_launched = false;                                  // ... and whether it is a frame twin: set where one is launched
+};
+// film_mode 2: workgroup-local float64 tile in LDS (needs 16x16-pixel workgroups: block_size >= 16)
+static mi_status atomic_film_tile(RenderFrame &F, const InitArgs &A, PathLaunch &PK) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const int film_mode = F.FP.film_mode; const uint32_t bs = F.bs, blocks_x = F.blocks_x, bs2_log2 = F.bs2_log2;
+    TileArgs &TA = PK.TA; size_t &tile_bytes = PK.tile_bytes;
+    memset(&TA, 0, sizeof TA);
+    tile_bytes = 0;
+    if (film_mode == 2 && bs >= 16) {
+        TA.tile_list = A.tile_list; TA.blocks_x = blocks_x; TA.bs = bs; TA.bs2_log2 = bs2_log2;
+        TA.side = 16u + 2u * std::max<uint32_t>((uint32_t) cfg->filter_border, (uint32_t) floorf(cfg->filter_radius + .5f));
+        TA.geom16 = (uint32_t) ((c->lds_bytes + 15) / 16);
+        tile_bytes = (size_t) TA.geom16 * 16 - c->lds_bytes + (size_t) TA.side * TA.side * MIW_FILM_CHANNELS * sizeof(double);
+        if (c->lds_bytes + tile_bytes > 64 * 1024) {
 #define MIW_ATOMIC_ATTR(T, M, A, I) HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_resident<false, T, M, A, I>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (c->lds_bytes + tile_bytes)));
-                MIW_ATOMIC_LIST(MIW_ATOMIC_ATTR)
+            MIW_ATOMIC_LIST(MIW_ATOMIC_ATTR)
 #undef MIW_ATOMIC_ATTR
-            }
         }
-        const uint32_t sync_every = 8;
-        uint32_t launches = 0;
-        bool place_stats_due = false;                              // (profile runs) the measuring launch's statistics, fetched after the last launch
-        // the film replay beside the render (overlap_prepare / overlap_enqueue above): frames replayed by k_film_lanes over the tile-interleaved log whose
-        // samples all run in ONE launch (a pixel is complete when that launch stores it), no placement, no time limit
-        // OPT-IN (MIW_FILM_OVERLAP=1): measured at C2 (gpurun r6k - r6m, profiles/r06_experiments.txt) it hides up to 3/4 of the replay and gains 0 - 1 % of the
-        // frame — the wave slots it needs cost the path kernel in proportion (32 workgroups short: +6 ms), a replay wavefront beside three packet-kernel
-        // wavefronts takes 20 - 30 ms instead of 5, and what is left after the path kernel cannot take less than one wavefront's chain (~8 - 10 ms)
-        const int overlap_mode = ropt.num("MIW_FILM_OVERLAP", 0);
-        const bool overlap = overlap_mode != 0 && c->overlap_state != 0 && film_mode == 1 && FP.rec16 && FP.film_lanes != 0 && FP.log_il != 0 && !place && !phased /* (QueueWork<..., Groups = false>) */ && tiny && c->diffuse_only && !MIW_SPECTRAL && !direct /* the 120-register packet kernel: the only one a replay wavefront fits beside */ &&
-                             per_launch >= cfg->spp && cfg->timeout_s <= 0.f && n_tiles > 0;
-        for (uint32_t done = 0; done < cfg->spp; ) {
-            uint32_t end = cfg->spp - done < per_launch ? cfg->spp : done + per_launch;
-            uint32_t feat_launched = FEAT_ALL;                       // the mask of the instantiation this launch IS: set where a lean twin is launched (MIW_DEBUG prints it)
-            bool frame_launched = false;                             // ... and whether it is a frame twin: set where one is launched
-            if (film_mode == 1) {
-                // persistent grid: <= 4 workgroups per CU, fed from the shared pixel queue
-                HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, c->d_next_pixel.n * sizeof(uint32_t), s));
-                rcfg.queues = 1u; Q.lane_cost = nullptr; Q.lane_sorted = nullptr; Q.piece_list = nullptr; Q.simd_ids = nullptr;
-                if (overlap && done == 0) {                          // the replay's arguments and the per-group counters, in front of the path kernel
-                    mi_status os = film_replay_setup(c, cfg, s, FP, n_tiles, bs, bs2_log2, blocks_x, blocks_y, replay);
-                    if (os == MI_OK) os = overlap_prepare(c, cfg, s, n_tiles, bs, blocks_x, Q, bs2_log2);
-                    if (os != MI_OK) return os;
-                    if (Q.group_done) HIP_TRY(c, hipEventRecord(c->ev_fork, s));
-                }
-                // chunk jobs (resident_kernel.h: QueueWork::fetch): full frames of the packet kernels, all samples in one launch. Without them a frame of N pixels
-                // on L resident lanes lasts ceil(N / L) rounds of one PIXEL (every lane starts at once, a pixel's samples are one serial job, the jobs are about
-                // equally long): C2 = 6.33 -> 7; with chunks of spp / 8 samples ceil(8 N / L) / 8 = 6.375.
-                Q.job_chunk = Q.job_pow = Q.job_total = 0u; Q.job_min = 0x80000000u;
-                // Every job costs one atomic on ONE address (the queue's counter) and a hand-over (a 16-byte state word out and in, past the L2): uniform chunks of
-                // 8 / 16 / 32 samples ran C2 in 702 / 496 / 305 ms, 64 / 128 / 256 in 226.8 / 226.5 / 230.6, whole pixels in 239.3 (gpurun r6p). So the chunks
-                // HALVE — a chunk ends where the samples still to do are a power of two — down to job_min samples (512 spp: 256 + 128 + 64 + 64): four hand-overs
-                // per pixel instead of eight, the tail as long as the smallest. The phase machine's full frames (C3, C4) take the same queue.
-                if ((tiny || (phased && MIW_PHASED_JOBS != 0)) && !pooled_fits && !place && !overlap && done == 0 && per_launch >= cfg->spp && cfg->timeout_s <= 0.f) {
-                    uint32_t jmin = tiny ? 64u : 32u;                                 // (gpurun r6s, halving chunks: C2 4 461 / 4 316 / 4 389 Msamples/s at 64 / 32 / 128; C3 1 298 / 1 305, C4 522 / 528 at 64 / 32)
-                    if (const char *e = ropt.get("MIW_JOB_CHUNK")) { const uint32_t v = (uint32_t) std::max(0, atoi(e)); jmin = (v & (v - 1u)) ? 0u : v; }
-                    // from 1.2 pixels per resident lane on (gpurun r6z, a rank's shard of C2 with / without: 4 ranks = 1.6 pixels per lane 67.8 / 79.1 ms, 5 ranks = 1.3: 58.7 / 67.5,
-                    // 6 ranks = 1.06: 54.9 / 54.6; at about ONE pixel per lane every pixel is in flight all the time and no lane finds a second job: 8 ranks 47.1 against the placed launches' 41.4)
-                    bool enough = (uint64_t) n_lanes * 5u >= (uint64_t) 6u * 64u * res_waves * n_simd;
-                    if (ropt.on("MIW_JOB_CHUNK_FORCE")) enough = true;
-                    uint32_t pow2 = 1u;
-                    while (pow2 * 2u < cfg->spp) pow2 *= 2u;                          // the largest power of two below spp
-                    uint64_t chunks = 1u;
-                    for (uint32_t r = pow2; jmin && r >= jmin && r < cfg->spp; r >>= 1) ++chunks;
-                    if (jmin && enough && chunks >= 2u && (uint64_t) n_lanes * chunks < (1ull << 31)) {
-                        Q.job_chunk = jmin; Q.job_min = jmin; Q.job_pow = pow2; Q.job_total = (uint32_t) ((uint64_t) n_lanes * chunks);
-                        K.job_chunk = jmin; K.job_chunks = (uint32_t) chunks;
-                    }
-                }
-                if (place && done == 0) { end = measure_end; Q.lane_cost = c->d_lane_cost.p; Q.simd_ids = c->d_simd_ids.p; }   // the measuring launch
-                else if (place) {
-                    // the lanes by what their pixel cost, dearest first (device radix sort), cut into pieces of 64: consecutive sorted lanes
-                    // (the pixels of a wavefront cost about the same and finish together), or every pieces-th one (one pixel of every cost
-                    // stratum per wavefront). Either way a piece's cost is that of its first (dearest) lane.
-                    HIP_TRY(c, rocprim::radix_sort_pairs_desc(c->d_place_tmp.p, place_tmp_bytes, c->d_lane_cost.p, c->d_cost_sorted.p, c->d_lane_iota.p, c->d_lane_sorted.p, (size_t) n_lanes, 0u, 32u, s));
-                    // Which cut: measured on rank 0's 1/8 shard (gpurun r4b, path kernel ms at 256 / 128 / 512 spp; no placement -> consecutive
-                    // -> spread): material balls 99.3 -> 90.7 -> 104.9, 0.9 M-triangle interior 130.8 -> 131.0 -> 120.9, Cornell packets
-                    // 40.0 -> 36.7 -> 44.3. Consecutive pieces keep the dear pixels in few wavefronts, which the priorities then favour; the
-                    // interior — every pixel dear, its walks bound by memory latency, tree and triangles beyond the L2s — gains from every
-                    // wavefront carrying the same mix. Rule: spread when the tree does not fit the aggregate L2 (32 MB). MIW_PLACE_SPREAD = 0 | 1 overrides.
-                    bool spread = phased && ((phased8 ? (size_t) c->nodes8_count * sizeof(Bvh8Node) : (size_t) c->nodes4_count * sizeof(Bvh4Node)) + (size_t) c->view.tri_count * sizeof(Tri)) > ((size_t) 32 << 20);
-                    if (const char *e = ropt.get("MIW_PLACE_SPREAD")) spread = atoi(e) != 0;
-                    Q.piece_a = spread ? 1u : 64u; Q.piece_b = spread ? n_pieces : 1u;
-                    // one host round trip between the measuring launch and the placed one, and only for the SIMD registry: the pieces' costs stay on the
-                    // device (the dealing below needs their ORDER only, which the sort fixed; round 6 — the statistics of the measuring launch,
-                    // mi_counters::place_*, are read after the frame's last launch, below)
-                    // the SIMDs the measuring launch ran on, numbered 0 .. nqueues - 1 (simd_ids[1 + hardware key]; word 0 = the "all dry" flag)
-                    std::vector<uint32_t> &ids = c->h_simd_ids;
-                    ids.resize(c->d_simd_ids.n);
-                    HIP_TRY(c, hipMemcpyAsync(ids.data(), c->d_simd_ids.p, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    HIP_TRY(c, hipStreamSynchronize(s));
-                    place_stats_due = cfg->profile != 0;
-                    uint32_t nqueues = 0;
-                    for (size_t k = 1; k < ids.size(); ++k) ids[k] = ids[k] ? nqueues++ : 0xffffffffu;
-                    ids[0] = 0u;
-                    if (nqueues < 2u || (uint64_t) nqueues * MIW_PLACE_PIECES < n_pieces) nqueues = 0;   // (cannot happen on a whole device; then: one queue)
-                    if (nqueues) {
-                    // The pieces arrive in descending cost (they are cuts of the sorted lane list), so "longest piece first onto the emptiest queue" is dealt
-                    // in rounds, alternating direction (round 0: piece i to queue i; round 1: piece N + i to queue N - 1 - i; ...): every queue gets one
-                    // piece of every cost stratum, dear and cheap strata paired. O(pieces) on the host between the two launches — the heap-based
-                    // longest-first dealing of rounds 3 - 5 took 0.3 ms there (4 096 pieces, 1 024 queues) with the GPU idle; any dealing renders the same film.
-                    std::vector<uint32_t> &list = c->h_piece_list;                                          // (context-owned: the upload below is not waited for)
-                    list.assign((size_t) nqueues * MIW_PLACE_PIECES, 0xffffffffu);
-                    for (uint32_t i = 0; i < n_pieces; ++i) {
-                        const uint32_t round = i / nqueues, k = i % nqueues, qd = (round & 1u) ? nqueues - 1u - k : k;
-                        list[(size_t) qd * MIW_PLACE_PIECES + round] = i;
-                    }
-                    HIP_TRY(c, c->d_piece_list.resize(list.size()));
-                    HIP_TRY(c, hipMemcpyAsync(c->d_piece_list.p, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                    HIP_TRY(c, hipMemcpyAsync(c->d_simd_ids.p, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                    rcfg.queues = nqueues; Q.piece_list = c->d_piece_list.p; Q.lane_sorted = c->d_lane_sorted.p; Q.simd_ids = c->d_simd_ids.p;
-                    K.placed = 1u;
-                    }
-                }
-                // persistent grid: as many workgroups per CU as the kernel is compiled for wavefronts per SIMD — the plain-diffuse packet kernel FIVE since
-                // round 6 (96 registers: 248.1 -> 238.3 ms at C2, resident_kernel.h), the other scalar_rgb packet kernels four. (Round 2 launched 3 per CU for shards of about one pixel per resident lane; with the
-                // least-progress-first priorities below every pixel of such a shard should start at once: 42.3 vs 49.6 ms on the 1/8
-                // shard of C2, profiles/r03.)
-                unsigned wg_per_cu = std::max(4u, direct ? 4u : (unsigned) res_waves);   // (never fewer than four: a kernel compiled for three keeps a fourth workgroup queued behind them)
-                if (const char *e = ropt.get("MIW_WG_PER_CU")) wg_per_cu = (unsigned) std::max(1, atoi(e));
-                unsigned room = 0u;                                // wave slots kept free for the replay that runs beside this launch (overlap_enqueue)
-                if (Q.group_done) { room = 32u; if (const char *e = ropt.get("MIW_FILM_OVERLAP_ROOM")) room = (unsigned) std::max(0, atoi(e)); }
-                // (room is counted from what is RESIDENT — the kernels compiled for three wavefronts per SIMD get a fourth workgroup per CU queued behind the
-                // first three, which would take every slot a shorter grid leaves)
-                const unsigned resident = (unsigned) c->cu_count * (direct ? (unsigned) MIW_DIRECT_WAVES : (unsigned) res_waves);
-                const unsigned full = room ? std::min((unsigned) c->cu_count * wg_per_cu, resident) : (unsigned) c->cu_count * wg_per_cu;
-                const dim3 pgrid(std::min<unsigned>(grid.x, full > 2u * room ? full - room : full));
-                // (`phased`, `trio_kernel`, `ph_waves`: decided above the loop; MIW_BVH4=0 keeps the BVH2 node body for the MATS_TRIO class: A/B runs)
-                K.path_kernel = phased ? (c->view.nodes4 ? 1u : 3u) : 0u;
-                const dim3 phgrid(std::min<unsigned>(grid.x, (unsigned) c->cu_count * (unsigned) ph_waves));
-                // the shade vote (phased_kernel.h): shade once n_shade * num >= den * (lanes of the busier walk body). Measured on the
-                // 4-wide tree (gpurun r2f / r2g, Msamples/s at 1 : 1 -> 3 : 2 -> 2 : 1): balls 844 -> 873 -> 860; interior with its
-                // environment-map lookups 338 -> 348 -> 361. MIW_SHADE_VOTE=num:den overrides (A/B runs).
-                // (per-XCD pixel queues — each XCD's workgroups taking their pixels from their own eighth of the image, so that the rays of
-                // one L2 stay in one region — measured neutral on the material balls, 883 vs 879 Msamples/s, and -2 % on the interior,
-                // 362 vs 370: the secondary rays of a closed room go everywhere. Removed again.)
-                // (rcfg.queues: 1, or the SIMD count for the placed launch of a small shard, set above)
-                // least-progress-first wave priorities (QueueWork::tick): the wavefronts of a SIMD finish together instead of the most
-                // expensive one running on alone. Made for shards of about one pixel per resident lane (1/8 of C2: path kernel 50.1 ->
-                // 42.3 ms; 1/8 of the material balls -14 %), it also shortens the drain of a full frame (C2 275.9 -> 268.7 ms), so it is
-                // always on — but for a packet kernel's launch of chunk jobs, whose tail is one chunk long: with and without them it took the same time in every configuration
-                // (r6t: C2 path kernel 222.01 221.47 ms with / 221.17 220.93 without, C5 573.9 / 573.5, direct 79.7 / 79.8), and the frame twins compile them out
-                // (kernel_pick.h: frame_twin). MIW_TAIL_PRIO = 0 | 1 overrides.
-                rcfg.tail_prio = tiny && Q.job_chunk ? 0u : 1u;
-                if (const char *e = ropt.get("MIW_TAIL_PRIO")) rcfg.tail_prio = atoi(e) != 0 ? 1u : 0u;
-                TraceLds ph_cfg = rcfg;
-                ph_cfg.shade_num = 2; ph_cfg.shade_den = c->have_env ? 4 : 3;
-                if (const char *e = ropt.get("MIW_SHADE_VOTE")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0) { ph_cfg.shade_num = (uint32_t) a; ph_cfg.shade_den = (uint32_t) b; } }
-                // when the walk loops hand over (phased_kernel.h): a loop runs on until its lanes are outnumbered 2 : 1 by the other walk body's, or
-                // node_exit : 1 / tri_exit : 1 by the lanes waiting for another body. Measured on the 8-wide walk (gpurun r5f - r5h, Msamples/s,
-                // material balls / interior): rounds 3 - 4's rule (1 : 1 against the other body, waiting + half the lanes that left) 1 119 / 463;
-                // 2 : 1 with node 1, triangle 1 -> 1 161 / 471; triangle 2 -> 1 174 / 472; node 2 -> 1 147 / 478; node 2, triangle 3 -> . / 481
-                // (the interior's shade runs are long: loops that wait for them less often win there). MIW_LOOP_EXIT=node:triangle overrides.
-                ph_cfg.node_exit = c->have_env ? 2u : 1u; ph_cfg.tri_exit = c->have_env ? 3u : 2u;
-                if (const char *e = ropt.get("MIW_LOOP_EXIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a >= 0 && b >= 0) { ph_cfg.node_exit = (uint32_t) a; ph_cfg.tri_exit = (uint32_t) b; } }
+    }
+    return MI_OK;
+}
+static mi_status launch_path_kernel(RenderFrame &F, const miw_pick::Facts &facts, const PathRoute &R, const RenderLds &L, PathLaunch &PK) {
+    mi_ctx *c = F.c; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s; const LaneQueues &Q = F.Q; LaunchTimer &T = F.T; mi_counters &K = F.K;
+    const uint32_t integ = R.direct ? INTEG_DIRECT : INTEG_PATH, feat = R.feat, res_waves = R.res_waves, end = PK.end;
+    const bool direct = R.direct, tiny = R.tiny, phased = R.phased, phased8 = R.phased8, place = R.place, packet_shard4 = R.packet_shard4, pooled = R.pooled;
+    const int ph_waves = R.ph_waves;
+    const size_t rlds = L.lay.rlds, rlds_plain = L.lay.rlds_plain, tile_bytes = PK.tile_bytes;
+    const dim3 grid = PK.grid, block(MIW_BLOCK); TraceLds &rcfg = PK.rcfg; const SceneView &view8 = PK.view8; const TileArgs &TA = PK.TA;
+    uint32_t &feat_launched = PK.feat_launched; bool &frame_launched = PK.frame_launched;
+    if (F.FP.film_mode == 1) {
+        // persistent grid: as many workgroups per CU as the kernel is compiled for wavefronts per SIMD — the plain-diffuse packet kernel FIVE since
+        // round 6 (96 registers: 248.1 -> 238.3 ms at C2, resident_kernel.h), the other scalar_rgb packet kernels four. (Round 2 launched 3 per CU for shards of about one pixel per resident lane; with the
+        // least-progress-first priorities below every pixel of such a shard should start at once: 42.3 vs 49.6 ms on the 1/8
+        // shard of C2, profiles/r03.)
+        unsigned wg_per_cu = miw_plan::persistent_wg_per_cu(direct, (unsigned) res_waves);   // (never fewer than four: a kernel compiled for three keeps a fourth workgroup queued behind them)
+        if (const char *e = ropt.get("MIW_WG_PER_CU")) wg_per_cu = (unsigned) std::max(1, atoi(e));
+        unsigned room = 0u;                                // wave slots kept free for the replay that runs beside this launch (overlap_enqueue)
+        if (Q.group_done) { room = 32u; if (const char *e = ropt.get("MIW_FILM_OVERLAP_ROOM")) room = (unsigned) std::max(0, atoi(e)); }
+        // (room is counted from what is RESIDENT — the kernels compiled for three wavefronts per SIMD get a fourth workgroup per CU queued behind the
+        // first three, which would take every slot a shorter grid leaves)
+        const dim3 pgrid(miw_plan::persistent_grid(grid.x, (unsigned) c->cu_count, wg_per_cu, room, direct ? (unsigned) MIW_DIRECT_WAVES : (unsigned) res_waves));
+        // (`phased`, `ph_waves`: path_route; MIW_BVH4=0 keeps the BVH2 node body for the MATS_TRIO class: A/B runs)
+        K.path_kernel = phased ? (c->view.nodes4 ? 1u : 3u) : 0u;
+        const dim3 phgrid(std::min<unsigned>(grid.x, (unsigned) c->cu_count * (unsigned) ph_waves));
+        // the shade vote (phased_kernel.h): shade once n_shade * num >= den * (lanes of the busier walk body). Measured on the
+        // 4-wide tree (gpurun r2f / r2g, Msamples/s at 1 : 1 -> 3 : 2 -> 2 : 1): balls 844 -> 873 -> 860; interior with its
+        // environment-map lookups 338 -> 348 -> 361. MIW_SHADE_VOTE=num:den overrides (A/B runs).
+        // (per-XCD pixel queues — each XCD's workgroups taking their pixels from their own eighth of the image, so that the rays of
+        // one L2 stay in one region — measured neutral on the material balls, 883 vs 879 Msamples/s, and -2 % on the interior,
+        // 362 vs 370: the secondary rays of a closed room go everywhere. Removed again.)
+        // (rcfg.queues: 1, or the SIMD count for the placed launch of a small shard, set above)
+        // least-progress-first wave priorities (QueueWork::tick): the wavefronts of a SIMD finish together instead of the most
+        // expensive one running on alone. Made for shards of about one pixel per resident lane (1/8 of C2: path kernel 50.1 ->
+        // 42.3 ms; 1/8 of the material balls -14 %), it also shortens the drain of a full frame (C2 275.9 -> 268.7 ms), so it is
+        // always on — but for a packet kernel's launch of chunk jobs, whose tail is one chunk long: with and without them it took the same time in every configuration
+        // (r6t: C2 path kernel 222.01 221.47 ms with / 221.17 220.93 without, C5 573.9 / 573.5, direct 79.7 / 79.8), and the frame twins compile them out
+        // (kernel_pick.h: frame_twin). MIW_TAIL_PRIO = 0 | 1 overrides.
+        rcfg.tail_prio = tiny && Q.job_chunk ? 0u : 1u;
+        if (const char *e = ropt.get("MIW_TAIL_PRIO")) rcfg.tail_prio = atoi(e) != 0 ? 1u : 0u;
+        TraceLds ph_cfg = rcfg;
+        ph_cfg.shade_num = 2; ph_cfg.shade_den = c->have_env ? 4 : 3;
+        if (const char *e = ropt.get("MIW_SHADE_VOTE")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a > 0 && b > 0) { ph_cfg.shade_num = (uint32_t) a; ph_cfg.shade_den = (uint32_t) b; } }
+        // when the walk loops hand over (phased_kernel.h): a loop runs on until its lanes are outnumbered 2 : 1 by the other walk body's, or
+        // node_exit : 1 / tri_exit : 1 by the lanes waiting for another body. Measured on the 8-wide walk (gpurun r5f - r5h, Msamples/s,
+        // material balls / interior): rounds 3 - 4's rule (1 : 1 against the other body, waiting + half the lanes that left) 1 119 / 463;
+        // 2 : 1 with node 1, triangle 1 -> 1 161 / 471; triangle 2 -> 1 174 / 472; node 2 -> 1 147 / 478; node 2, triangle 3 -> . / 481
+        // (the interior's shade runs are long: loops that wait for them less often win there). MIW_LOOP_EXIT=node:triangle overrides.
+        ph_cfg.node_exit = c->have_env ? 2u : 1u; ph_cfg.tri_exit = c->have_env ? 3u : 2u;
+        if (const char *e = ropt.get("MIW_LOOP_EXIT")) { int a = 0, b = 0; if (sscanf(e, "%d:%d", &a, &b) == 2 && a >= 0 && b >= 0) { ph_cfg.node_exit = (uint32_t) a; ph_cfg.tri_exit = (uint32_t) b; } }
 // (the Spec argument is a constant of the build, phased_kernel.h: MIW_DEBUG's line gives its value, the other five arguments as the macro got them)
 #define MIW_PHASED_LAUNCH_(M, A, WV, W, PL) do { MIW_SAY_KERNEL_TEXT(ropt, MIW_PHASE_SPEC != 0 ? "k_path_phased<" #M ", " #A ", true, " #WV ", " #W ", " #PL ">" : "k_path_phased<" #M ", " #A ", false, " #WV ", " #W ", " #PL ">"); \
     MIW_TIMED(6, hipLaunchKernelGGL((k_path_phased<M, A, MIW_PHASE_SPEC != 0, WV, W, PL>), phgrid, block, rlds, s, P, (W) == 2 ? view8 : c->view, Q, c->d_cnt.p, ph_cfg, end, c->d_next_pixel.p)); } while (0)
 #define MIW_PHASED_LAUNCH(M, A, W) do { if (ph_waves == 4) MIW_PHASED_LAUNCH_(M, A, 4, W, false); else MIW_PHASED_LAUNCH_(M, A, 3, W, false); } while (0)
-                K.tree_width = phased ? (phased8 ? 8u : (c->view.nodes4 ? 4u : 2u)) : 0u;
+        K.tree_width = phased ? (phased8 ? 8u : (c->view.nodes4 ? 4u : 2u)) : 0u;
 #if MIW_SPECTRAL
-                const bool pooled = false;
-                if (pooled) { }
+        if (pooled) { }
 #else
-                const bool pooled = phased8 && !place && pooled_fits;
-                if (pooled) {
-                    // one workgroup per CU; the vote's constants travel in the fields the old kernel's vote used (pooled_kernel.h: shade_min, walk_min, node_min, tri_min)
-                    // + pool_claim_min; MIW_POOL_VOTE=shade_min:walk_min:node_min:tri_min:claim_min overrides (A/B runs)
-                    TraceLds pcfg = layp.cfg; pcfg.queues = 1u; pcfg.tail_prio = ph_cfg.tail_prio;
-                    pcfg.shade_num = 48; pcfg.shade_den = 16; pcfg.node_exit = 40u; pcfg.tri_exit = 20u; pcfg.pool_claim_min = 8u;
-                    if (const char *e = ropt.get("MIW_POOL_VOTE")) { int a = 0, b = 0, n = 0, t = 0, m = 0; if (sscanf(e, "%d:%d:%d:%d:%d", &a, &b, &n, &t, &m) == 5 && a > 0 && b >= 0) { pcfg.shade_num = (uint32_t) a; pcfg.shade_den = (uint32_t) b; pcfg.node_exit = (uint32_t) n; pcfg.tri_exit = (uint32_t) t; pcfg.pool_claim_min = (uint32_t) std::max(m, 1); } }
-                    const unsigned NL = (unsigned) pool_nw * 64u;
-                    const dim3 qgrid(std::min<unsigned>((n_lanes + NL - 1u) / NL, (unsigned) c->cu_count)), qblock(NL);
-                    SceneView pview = view8;
-                    if (c->lights_on) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with point / spot / directional / constant emitters");
-                    if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
-                    const miw_pick::Pick pick = miw_pick::tree_class(facts);
+        if (pooled) {
+            const int pool_nw = L.pool_nw, pool_pp = L.pool_pp; const LdsLayout &layp = L.layp;
+            // one workgroup per CU; the vote's constants travel in the fields the old kernel's vote used (pooled_kernel.h: shade_min, walk_min, node_min, tri_min)
+            // + pool_claim_min; MIW_POOL_VOTE=shade_min:walk_min:node_min:tri_min:claim_min overrides (A/B runs)
+            TraceLds pcfg = layp.cfg; pcfg.queues = 1u; pcfg.tail_prio = ph_cfg.tail_prio;
+            pcfg.shade_num = 48; pcfg.shade_den = 16; pcfg.node_exit = 40u; pcfg.tri_exit = 20u; pcfg.pool_claim_min = 8u;
+            if (const char *e = ropt.get("MIW_POOL_VOTE")) { int a = 0, b = 0, n = 0, t = 0, m = 0; if (sscanf(e, "%d:%d:%d:%d:%d", &a, &b, &n, &t, &m) == 5 && a > 0 && b >= 0) { pcfg.shade_num = (uint32_t) a; pcfg.shade_den = (uint32_t) b; pcfg.node_exit = (uint32_t) n; pcfg.tri_exit = (uint32_t) t; pcfg.pool_claim_min = (uint32_t) std::max(m, 1); } }
+            const unsigned NL = (unsigned) pool_nw * 64u;
+            const dim3 qgrid(std::min<unsigned>((F.n_lanes + NL - 1u) / NL, (unsigned) c->cu_count)), qblock(NL);
+            if (c->lights_on) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with point / spot / directional / constant emitters");
+            if (c->nested) return fail(c, MI_ERR_INVALID, "render: the pooled kernel (MI_PATH_KERNEL_POOLED) does not serve scenes with mask / blendbsdf / null / thindielectric records");
+            const miw_pick::Pick pick = miw_pick::tree_class(facts);
 #define MIW_POOLED_LAUNCH(M, A, NW_, PP_) if (pick.mats == (M) && pick.analytic == (A) && pool_nw == (NW_) && pool_pp == (PP_)) { \
-                        HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
-                        MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, pview, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } else
-                    MIW_POOLED_LIST(MIW_POOLED_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_pooled<%d, %d, %d, %d> in the library", pick.mats, (int) pick.analytic, pool_nw, pool_pp);
+                HIP_TRY(c, hipFuncSetAttribute((const void *) k_path_pooled<M, A, NW_, PP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) layp.rlds)); \
+                MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_pooled<M, A, NW_, PP_>), qgrid, qblock, layp.rlds, s, P, view8, Q, c->d_cnt.p, pcfg, end, c->d_next_pixel.p)); } else
+            MIW_POOLED_LIST(MIW_POOLED_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_pooled<%d, %d, %d, %d> in the library", pick.mats, (int) pick.analytic, pool_nw, pool_pp);
 #undef MIW_POOLED_LAUNCH
-                    K.pooled = 1u; K.pool_waves = (uint32_t) pool_nw;
-                }
+            K.pooled = 1u; K.pool_waves = (uint32_t) pool_nw;
+        }
 #endif
-                else
-                if (phased && !c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);    // (MIW_BVH4=0: the phase machine steps through the BVH2, the MATS_TRIO class only)
-                else if (phased) {
-                    // the tree's width, and the Placed instantiations for a shard of about one pixel per resident lane (measuring, then placed launch)
-                    const miw_pick::Pick pick = miw_pick::tree_class(facts);
-                    const int wide = phased8 ? 2 : 1;
+        else
+        if (phased && !c->view.nodes4) MIW_PHASED_LAUNCH(MATS_TRIO, false, 0);    // (MIW_BVH4=0: the phase machine steps through the BVH2, the MATS_TRIO class only)
+        else if (phased) {
+            // the tree's width, and the Placed instantiations for a shard of about one pixel per resident lane (measuring, then placed launch)
+            const miw_pick::Pick pick = miw_pick::tree_class(facts);
+            const int wide = phased8 ? 2 : 1;
 #define MIW_PHASED_PICKED(M, A, WV, W, PL) if (pick.mats == (M) && pick.analytic == (A) && ph_waves == (WV) && wide == (W) && place == (PL)) MIW_PHASED_LAUNCH_(M, A, WV, W, PL); else
-                    MIW_PHASED_LIST(MIW_PHASED_PICKED) return fail(c, MI_ERR_STATE, "render: no k_path_phased<%d, %d, ., %d, %d, %d> in the library", pick.mats, (int) pick.analytic, ph_waves, wide, (int) place);
+            MIW_PHASED_LIST(MIW_PHASED_PICKED) return fail(c, MI_ERR_STATE, "render: no k_path_phased<%d, %d, ., %d, %d, %d> in the library", pick.mats, (int) pick.analytic, ph_waves, wide, (int) place);
 #undef MIW_PHASED_PICKED
-                }
+        }
 #undef MIW_PHASED_LAUNCH
 #undef MIW_PHASED_LAUNCH_
-                // (MIW_DEBUG's line is the text of the template-id the launch instantiates: MIW_LAUNCH_NAMED)
+        // (MIW_DEBUG's line is the text of the template-id the launch instantiates: MIW_LAUNCH_NAMED)
 #define MIW_PACKET_SPECIAL(...) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (__VA_ARGS__), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p))
-                // the special instantiations of the packet kernel, in front of its table (none of them is ever the direct integrator's: `overlap` and `packet_shard4` above)
-                else if (Q.group_done && c->view.tri_count <= 32u)     // (overlap: tiny && diffuse_only) the instantiation that counts finished pixels per group of 64 tiles
-                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>);
-                else if (Q.group_done)
-                    MIW_PACKET_SPECIAL(k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>);
-                else if (packet_shard4 && !Q.group_done && feat == FEAT_NONE) {
-                    feat_launched = FEAT_NONE;
-                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4, FEAT_NONE>);
-                }
-                else if (packet_shard4 && !Q.group_done)
-                    MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>);
+        // the special instantiations of the packet kernel, in front of its table (none of them is ever the direct integrator's: `overlap` and `packet_shard4` above)
+        else if (Q.group_done && c->view.tri_count <= 32u)     // (overlap: tiny && diffuse_only) the instantiation that counts finished pixels per group of 64 tiles
+            MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, true>);
+        else if (Q.group_done)
+            MIW_PACKET_SPECIAL(k_path_resident<true, 1, MATS_DIFFUSE, false, INTEG_PATH, true>);
+        else if (packet_shard4 && !Q.group_done && feat == FEAT_NONE) {
+            feat_launched = FEAT_NONE;
+            MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4, FEAT_NONE>);
+        }
+        else if (packet_shard4 && !Q.group_done)
+            MIW_PACKET_SPECIAL(k_path_resident<true, 2, MATS_DIFFUSE, false, INTEG_PATH, false, 4>);
 #undef MIW_PACKET_SPECIAL
-                else {
-                    // kernel variants (kernel_pick.h): no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that variant fits 4 waves per
-                    // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
-                    const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, false);
-                    // (the lean twins in front of the table: a mask that is no instantiation has become FEAT_ALL above, a class without a twin keeps the full kernel)
-                    // (... and the frame twins in front of those: a lean twin's launch whose facts are the ones the twin has compiled in — chunk jobs from one queue, the 16-byte
-                    // log, no tail priorities, the leaf filter on, no group counts; MIW_FRAME_TWIN=0 keeps the lean twin)
-                    miw_pick::LaunchFacts lf;
-                    lf.job_chunks = Q.job_chunk != 0u; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = rcfg.queues == 1u; lf.tail_prio = rcfg.tail_prio != 0u;
-                    lf.leaf_filter = c->lds_cfg.leaves != 0u; lf.group_counts = Q.group_done != nullptr;
-                    const bool frame = miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
+        else {
+            // kernel variants (kernel_pick.h): no BSDF dispatch when every shape is plain diffuse (64-bit candidate masks: that variant fits 4 waves per
+            // SIMD without spills); else 32-bit candidate masks up to 32 triangles. The packet kernels stage the scene's tables (rlds), the lock-step tree kernels do not.
+            const miw_pick::Pick pick = direct ? miw_pick::resident_direct(facts) : miw_pick::resident_path(facts, false);
+            // (the lean twins in front of the table: a mask that is no instantiation has become FEAT_ALL above, a class without a twin keeps the full kernel)
+            // (... and the frame twins in front of those: a lean twin's launch whose facts are the ones the twin has compiled in — chunk jobs from one queue, the 16-byte
+            // log, no tail priorities, the leaf filter on, no group counts; MIW_FRAME_TWIN=0 keeps the lean twin)
+            miw_pick::LaunchFacts lf;
+            lf.job_chunks = Q.job_chunk != 0u; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = rcfg.queues == 1u; lf.tail_prio = rcfg.tail_prio != 0u;
+            lf.leaf_filter = c->lds_cfg.leaves != 0u; lf.group_counts = Q.group_done != nullptr;
+            const bool frame = miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
 #define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
-                    MIW_LEAN_LIST(MIW_FRAME_LAUNCH)
+            MIW_LEAN_LIST(MIW_FRAME_LAUNCH)
 #undef MIW_FRAME_LAUNCH
 #define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
-                    MIW_LEAN_LIST(MIW_LEAN_LAUNCH)
+            MIW_LEAN_LIST(MIW_LEAN_LAUNCH)
 #undef MIW_LEAN_LAUNCH
 #define MIW_RESIDENT_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, A, I>), pgrid, block, (T) != 0 ? rlds : rlds_plain, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); else
-                    MIW_RESIDENT_LIST(MIW_RESIDENT_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<true, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
+            MIW_RESIDENT_LIST(MIW_RESIDENT_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<true, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_RESIDENT_LAUNCH
-                }
-            } else {
-                // the float64-atomics film: one workgroup per 16 x 16 pixels, three classes (kernel_pick.h: resident_atomic)
-                const miw_pick::Pick pick = miw_pick::resident_atomic(facts);
+        }
+    } else {
+        // the float64-atomics film: one workgroup per 16 x 16 pixels, three classes (kernel_pick.h: resident_atomic)
+        const miw_pick::Pick pick = miw_pick::resident_atomic(facts);
 #define MIW_ATOMIC_LAUNCH(T, M, A, I) if (integ == (I) && MIW_PICKED(T, M, A)) MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<false, T, M, A, I>), grid, block, c->lds_bytes + tile_bytes, s, P, c->view, Q, c->d_accum.p, c->d_cnt.p, c->lds_cfg, end, TA, (uint32_t *) nullptr)); else
-                MIW_ATOMIC_LIST(MIW_ATOMIC_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<false, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
+        MIW_ATOMIC_LIST(MIW_ATOMIC_LAUNCH) return fail(c, MI_ERR_STATE, "render: no k_path_resident<false, %d, %d, %d, %u> in the library", pick.tiny, pick.mats, (int) pick.analytic, integ);
 #undef MIW_ATOMIC_LAUNCH
+    }
+    return MI_OK;
+}
+
+// ---- mi_render, the resident plan: every pixel advances `per_launch` samples per launch ----
+static mi_status render_resident(RenderFrame &F, const miw_pick::Facts &facts, const RenderLds &L, FilmReplay &replay, mi_status &result) {
+    mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s;
+    LaneQueues &Q = F.Q; LaunchTimer &T = F.T; mi_counters &K = F.K; const int film_mode = F.FP.film_mode;
+    PathLaunch PK; PK.grid = dim3((F.n_lanes + MIW_BLOCK - 1) / MIW_BLOCK);
+    const InitArgs A = init_args(F);
+    MIW_TIMED(3, hipLaunchKernelGGL(k_init_pixels, PK.grid, dim3(MIW_BLOCK), 0, s, P, c->q_st.p, c->q_pixel.p, A));
+    HIP_TRY(c, hipGetLastError());
+    PathRoute R;
+    MI_TRY(path_route(F, facts, L, R));
+    HIP_TRY(c, c->d_next_pixel.resize(std::max<uint32_t>(8u, R.n_simd)));
+    PK.rcfg = L.lay.cfg;
+    PK.view8 = R.phased8 ? view_over_tree8(c) : c->view;
+    size_t place_tmp_bytes = 0;
+    if (R.place) MI_TRY(place_prepare(F, R, place_tmp_bytes));
+    MI_TRY(atomic_film_tile(F, A, PK));
+    const uint32_t sync_every = 8;
+    uint32_t launches = 0;
+    bool place_stats_due = false;                              // (profile runs) the measuring launch's statistics, fetched after the last launch
+    for (uint32_t done = 0; done < cfg->spp; ) {
+        PK.end = cfg->spp - done < R.per_launch ? cfg->spp : done + R.per_launch;
+        PK.feat_launched = FEAT_ALL; PK.frame_launched = false;
+        if (film_mode == 1) {
+            // persistent grid: <= 4 workgroups per CU, fed from the shared pixel queue
+            HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, c->d_next_pixel.n * sizeof(uint32_t), s));
+            PK.rcfg.queues = 1u; Q.lane_cost = nullptr; Q.lane_sorted = nullptr; Q.piece_list = nullptr; Q.simd_ids = nullptr;
+            if (R.overlap && done == 0) {                        // the replay's arguments and the per-group counters, in front of the path kernel
+                MI_TRY(film_replay_setup(F, replay));
+                MI_TRY(overlap_prepare(F));
+                if (Q.group_done) HIP_TRY(c, hipEventRecord(c->ev_fork, s));
             }
-            if (Q.group_done) {                                      // the path kernel is in `s`: queue the replay beside it
-                const mi_status os = overlap_enqueue(c, ropt, P, s, T, replay, n_tiles, overlap_mode != 2);
-                if (os != MI_OK) return os;
-                if (c->replay_enqueued) { K.film_overlapped = 1u; K.film_groups = c->replay_launches; }
-                Q.group_done = nullptr; Q.group_expected = nullptr; Q.group_flag = nullptr;
+            chunk_jobs(F, R, L, done);
+            if (R.place && done == 0) { PK.end = R.measure_end; Q.lane_cost = c->d_lane_cost.p; Q.simd_ids = c->d_simd_ids.p; }   // the measuring launch
+            else if (R.place) MI_TRY(place_deal(F, R, place_tmp_bytes, PK.rcfg, place_stats_due));                               // the placed launch
+        }
+        MI_TRY(launch_path_kernel(F, facts, R, L, PK));
+        if (Q.group_done) {                                      // the path kernel is in `s`: queue the replay beside it
+            MI_TRY(overlap_enqueue(F, replay, R.overlap_mode != 2));
+            if (c->replay_enqueued) { K.film_overlapped = 1u; K.film_groups = c->replay_launches; }
+            Q.group_done = nullptr; Q.group_expected = nullptr; Q.group_flag = nullptr;
+        }
+        // which instantiation this launch was, said after the launch site set it: 0x0 only where a lean twin (FEAT_NONE) was launched — not for a class without
+        // a twin, the overlap's Groups = true pair, the direct integrator or the float64-atomics film, which run the full kernel whatever mask was chosen
+        if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased) fprintf(stderr, "[miwave] packet path kernel launched: scene features 0x%x of 0x%x compiled in (mask chosen for the render: 0x%x)\n", PK.feat_launched, (uint32_t) FEAT_ALL, R.feat);
+        if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased) fprintf(stderr, "[miwave] packet path kernel launched: frame twin %s\n", PK.frame_launched ? "yes (chunk jobs, one queue, 16-byte log, no tail priorities, leaf filter compiled in)" : "no");
+        K.n_path++; K.iterations++;
+        done = PK.end;
+        // cancel() / timeout take effect at launch granularity (the reference checks should_stop() per block)
+        if ((++launches % sync_every == 0 || cfg->timeout_s > 0.f || c->cancel.load()) && done < cfg->spp) {
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(s));
+            T.drain();
+            if (c->cancel.load() || out_of_time(F)) { result = MI_ERR_CANCELLED; break; }
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    Counters sum;
+    MI_TRY(read_counters(F, sum));
+    MI_TRY(place_statistics(F, R, place_stats_due));
+    print_debug_statistics(c, ropt, K);                      // (debug builds only: -DMIW_PHASE_STATS / _WALK_STATS / _SECTION_PROFILE / _VERIFY_FILTER)
+    T.drain();
+    return MI_OK;
+}
+
+#if !MIW_SPECTRAL
+// ---- mi_render, the wavefront (queue) plan: one launch per stage and iteration over work lists; the stackless fallback ----
+static mi_status render_wavefront(RenderFrame &F, mi_status &result) {
+    mi_ctx *c = F.c; const Options &ropt = F.ropt; const RenderParams &P = F.P; hipStream_t s = F.s;
+    const LaneQueues &Q = F.Q; LaunchTimer &T = F.T; mi_counters &K = F.K; const int film_mode = F.FP.film_mode; const uint32_t n_lanes = F.n_lanes;
+    dim3 grid((n_lanes + MIW_BLOCK - 1) / MIW_BLOCK), block(MIW_BLOCK);
+    const InitArgs A = init_args(F);
+    // work lists (stream compaction + material sorting), double-buffered by iteration parity
+    const size_t n_wg = grid.x, seg_lanes = n_wg * MIW_BLOCK;
+    HIP_TRY(c, c->d_lists.resize((size_t) 2 * WL_LISTS * seg_lanes));
+    HIP_TRY(c, c->d_list_counts.resize(2 * WL_LISTS * n_wg));
+    HIP_TRY(c, hipMemsetAsync(c->d_list_counts.p, 0, 2 * WL_LISTS * n_wg * sizeof(uint32_t), s));
+    WorkLists WL[2];
+    for (int p = 0; p < 2; ++p) {
+        for (int l = 0; l < WL_LISTS; ++l) WL[p].list[l] = c->d_lists.p + ((size_t) p * WL_LISTS + l) * seg_lanes;
+        WL[p].count = c->d_list_counts.p + (size_t) p * WL_LISTS * n_wg;
+    }
+    MIW_TIMED(3, hipLaunchKernelGGL(k_init_lanes, grid, block, 0, s, P, Q, c->q_pixel.p, A, WL[0]));
+    HIP_TRY(c, hipGetLastError());
+
+    // trees walked with the LDS stack: one persistent stream kernel serves the E and the S rays of an iteration
+    // (device/stream_trace.h); MIW_STREAM=0 keeps the slice-per-workgroup kernels (A/B runs)
+    const bool stream_on = !ropt.off("MIW_STREAM");
+    const bool stream = stream_on && c->lds_cfg.stack && !c->lds_cfg.brute && c->lds_cfg.nodes_staged == 0;
+    K.path_kernel = stream ? 2u : 0u;
+    // round 6: the stream kernel walks the 8-wide tree (the phase machine's two walk bodies) wherever mi_bvh_build produced it; its hit records then
+    // name triangles in that tree's order, so k_sort_hits and k_shade get the view with the triangles / vertex normals of that order
+    const bool stream8 = stream && tree8_on(c, ropt);
+    const SceneView pview = stream8 ? view_over_tree8(c) : c->view;
+    K.tree_width = stream8 ? 8u : 0u;
+    if (stream) {
+        HIP_TRY(c, c->d_next_pixel.resize(1));
+        HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, sizeof(uint32_t), s));
+    }
+    const dim3 sgrid(std::min<unsigned>(grid.x, (unsigned) c->cu_count * (stream8 ? 4u : (unsigned) MIW_STREAM_WAVES)));
+    const int check_every = 16;
+    bool first = true;
+    unsigned long long active_prev = 0;
+    uint32_t parity = 0;
+    for (;;) {
+        for (int it = 0; it < check_every; ++it, parity ^= 1u) {
+            const WorkLists &cur = WL[parity], &nxt = WL[parity ^ 1u];
+            if (stream) {
+                if (stream8) MIW_TIMED(0, hipLaunchKernelGGL(k_trace_stream<2>, sgrid, block, c->lds_bytes, s, pview, Q, c->lds_cfg, cur, (uint32_t) n_wg, c->d_next_pixel.p));
+                else MIW_TIMED(0, hipLaunchKernelGGL(k_trace_stream<0>, sgrid, block, c->lds_bytes, s, pview, Q, c->lds_cfg, cur, (uint32_t) n_wg, c->d_next_pixel.p));
+                MIW_TIMED(1, hipLaunchKernelGGL(k_sort_hits, grid, block, 0, s, pview, Q, cur, c->d_next_pixel.p));
+                K.n_trace_closest++; K.n_trace_any++;
+            } else {
+                if (!first) {
+                    MIW_TIMED(1, hipLaunchKernelGGL(k_trace<true>, grid, block, c->lds_bytes, s, c->view, Q, c->lds_cfg, cur));
+                    K.n_trace_any++;
+                }
+                MIW_TIMED(0, hipLaunchKernelGGL(k_trace<false>, grid, block, c->lds_bytes, s, c->view, Q, c->lds_cfg, cur));
+                K.n_trace_closest++;
             }
-            // which instantiation this launch was, said after the launch site set it: 0x0 only where a lean twin (FEAT_NONE) was launched — not for a class without
-            // a twin, the overlap's Groups = true pair, the direct integrator or the float64-atomics film, which run the full kernel whatever mask was chosen
-            if (ropt.get("MIW_DEBUG") && tiny && !phased) fprintf(stderr, "[miwave] packet path kernel launched: scene features 0x%x of 0x%x compiled in (mask chosen for the render: 0x%x)\n", feat_launched, (uint32_t) FEAT_ALL, feat);
-            if (ropt.get("MIW_DEBUG") && tiny && !phased) fprintf(stderr, "[miwave] packet path kernel launched: frame twin %s\n", frame_launched ? "yes (chunk jobs, one queue, 16-byte log, no tail priorities, leaf filter compiled in)" : "no");
-            K.n_path++; K.iterations++;
-            done = end;
-            // cancel() / timeout take effect at launch granularity (the reference checks should_stop() per block)
-            if ((++launches % sync_every == 0 || cfg->timeout_s > 0.f || c->cancel.load()) && done < cfg->spp) {
-                HIP_TRY(c, hipGetLastError());
-                HIP_TRY(c, hipStreamSynchronize(s));
-                T.drain();
-                if (c->cancel.load() || out_of_time()) { result = MI_ERR_CANCELLED; break; }
-            }
+            const uint32_t count_active = it == check_every - 1 ? 1u : 0u;
+            if (film_mode == 1)
+                MIW_TIMED(2, hipLaunchKernelGGL(k_shade<true>, grid, block, 0, s, P, pview, Q, (double *) nullptr, c->d_cnt.p, count_active, cur, nxt));
+            else
+                MIW_TIMED(2, hipLaunchKernelGGL(k_shade<false>, grid, block, 0, s, P, pview, Q, c->d_accum.p, c->d_cnt.p, count_active, cur, nxt));
+            K.n_shade++; K.iterations++;
+            first = false;
         }
         HIP_TRY(c, hipGetLastError());
         Counters sum;
-        mi_status rs = read_counters(sum);
-        if (rs != MI_OK) return rs;
-        if (place_stats_due) {             // what the measuring launch found (mi_counters::place_*): the shard's dearest pixel and the mean
-            std::vector<uint32_t> all(n_lanes); uint32_t first_lane = 0, px = 0;
-            HIP_TRY(c, hipMemcpyAsync(all.data(), c->d_cost_sorted.p, (size_t) n_lanes * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipMemcpyAsync(&first_lane, c->d_lane_sorted.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            if (first_lane < n_lanes) HIP_TRY(c, hipMemcpy(&px, c->q_pixel.p + first_lane, sizeof(uint32_t), hipMemcpyDeviceToHost));
-            double csum = 0.0; uint32_t with = 0;
-            for (uint32_t v : all) if (v) { csum += (double) v; ++with; }
-            K.place_cost_max = all.empty() ? 0u : all[0]; K.place_cost_mean = with ? csum / with : 0.0; K.place_max_pixel = px;
-            K.place_cost_unit = phased ? 1u : 0u; K.place_measure_spp = measure_end;
-        }
-        if (K.placed && ropt.get("MIW_DEBUG")) {                     // how the placed launch went: SIMDs that registered, lanes handed out per queue
-            std::vector<uint32_t> cur(n_simd), ids(1u + (1u << 14)), cost(n_pieces);
-            (void) hipMemcpy(cur.data(), c->d_next_pixel.p, n_simd * sizeof(uint32_t), hipMemcpyDeviceToHost);
-            (void) hipMemcpy(ids.data(), c->d_simd_ids.p, ids.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-            (void) hipMemcpy2D(cost.data(), sizeof(uint32_t), c->d_cost_sorted.p, Q.piece_a * sizeof(uint32_t), sizeof(uint32_t), n_pieces, hipMemcpyDeviceToHost);
-            uint32_t keys = 0, key_or = 0, full = 0, over = 0; uint64_t csum = 0; uint32_t cmin = ~0u, cmax = 0;
-            for (uint32_t k = 0; k < (1u << 14); ++k) if (ids[1 + k] != 0xffffffffu) { ++keys; key_or |= k; }
-            ids[0] = keys;
-            for (uint32_t v : cur) { full += v >= 64u * MIW_PLACE_PIECES; over += v > 64u * MIW_PLACE_PIECES; }
-            for (uint32_t v : cost) { csum += v; cmin = std::min(cmin, v); cmax = std::max(cmax, v); }
-            fprintf(stderr, "[miwave] placed queues: %u SIMDs numbered, %u distinct hardware keys (bits used 0x%x), %u of %u queues drained (%u asked beyond their end), "
-                            "cost of the dearest pixel of a piece min / mean / max = %u / %.0f / %u (iterations, or 256-cycle units)\n", ids[0], keys, key_or, full, n_simd, over, cmin, (double) csum / n_pieces, cmax);
-        }
-        print_debug_statistics(c, ropt, K);                      // (debug builds only: -DMIW_PHASE_STATS / _WALK_STATS / _SECTION_PROFILE / _VERIFY_FILTER)
+        MI_TRY(read_counters(F, sum));
         T.drain();
+        // active_lanes accumulates over the counting launches: the last one's share is the delta
+        unsigned long long active_now = sum.active_lanes - active_prev;
+        active_prev = sum.active_lanes;
+        if (active_now == 0) break;
+        if (c->cancel.load()) { result = MI_ERR_CANCELLED; break; }
+        if (out_of_time(F)) { result = MI_ERR_CANCELLED; break; }
     }
-#if !MIW_SPECTRAL
-    else if (n_lanes > 0) {
-        dim3 grid((n_lanes + MIW_BLOCK - 1) / MIW_BLOCK), block(MIW_BLOCK);
-        InitArgs A; A.block_ids = c->d_block_ids.p; A.tile_list = cfg->tile_list ? c->d_tile_list.p : nullptr;
-        A.blocks_x = blocks_x; A.blocks_y = blocks_y; A.bs = bs; A.bs2_log2 = bs2_log2; A.base_seed = cfg->base_seed;
-        // work lists (stream compaction + material sorting), double-buffered by iteration parity
-        const size_t n_wg = grid.x, seg_lanes = n_wg * MIW_BLOCK;
-        HIP_TRY(c, c->d_lists.resize((size_t) 2 * WL_LISTS * seg_lanes));
-        HIP_TRY(c, c->d_list_counts.resize(2 * WL_LISTS * n_wg));
-        HIP_TRY(c, hipMemsetAsync(c->d_list_counts.p, 0, 2 * WL_LISTS * n_wg * sizeof(uint32_t), s));
-        WorkLists WL[2];
-        for (int p = 0; p < 2; ++p) {
-            for (int l = 0; l < WL_LISTS; ++l) WL[p].list[l] = c->d_lists.p + ((size_t) p * WL_LISTS + l) * seg_lanes;
-            WL[p].count = c->d_list_counts.p + (size_t) p * WL_LISTS * n_wg;
-        }
-        MIW_TIMED(3, hipLaunchKernelGGL(k_init_lanes, grid, block, 0, s, P, Q, c->q_pixel.p, A, WL[0]));
-        HIP_TRY(c, hipGetLastError());
-
-        // trees walked with the LDS stack: one persistent stream kernel serves the E and the S rays of an iteration
-        // (device/stream_trace.h); MIW_STREAM=0 keeps the slice-per-workgroup kernels (A/B runs)
-        const bool stream_on = !ropt.off("MIW_STREAM");
-        const bool stream = stream_on && c->lds_cfg.stack && !c->lds_cfg.brute && c->lds_cfg.nodes_staged == 0;
-        K.path_kernel = stream ? 2u : 0u;
-        // round 6: the stream kernel walks the 8-wide tree (the phase machine's two walk bodies) wherever mi_bvh_build produced it; its hit records then
-        // name triangles in that tree's order, so k_sort_hits and k_shade get the view with the triangles / vertex normals of that order
-        const bool stream8 = stream && tree8_on(c, ropt);
-        SceneView pview = c->view;
-        if (stream8) { pview.nodes8 = c->d_nodes8.p; pview.tris = c->d_tris8.p; if (pview.tri_vn) pview.tri_vn = c->d_tri_vn8.p; }
-        K.tree_width = stream8 ? 8u : 0u;
-        if (stream) {
-            HIP_TRY(c, c->d_next_pixel.resize(1));
-            HIP_TRY(c, hipMemsetAsync(c->d_next_pixel.p, 0, sizeof(uint32_t), s));
-        }
-        const dim3 sgrid(std::min<unsigned>(grid.x, (unsigned) c->cu_count * (stream8 ? 4u : (unsigned) MIW_STREAM_WAVES)));
-        const int check_every = 16;
-        bool first = true;
-        unsigned long long active_prev = 0;
-        uint32_t parity = 0;
-        for (;;) {
-            for (int it = 0; it < check_every; ++it, parity ^= 1u) {
-                const WorkLists &cur = WL[parity], &nxt = WL[parity ^ 1u];
-                if (stream) {
-                    if (stream8) MIW_TIMED(0, hipLaunchKernelGGL(k_trace_stream<2>, sgrid, block, c->lds_bytes, s, pview, Q, c->lds_cfg, cur, (uint32_t) n_wg, c->d_next_pixel.p));
-                    else MIW_TIMED(0, hipLaunchKernelGGL(k_trace_stream<0>, sgrid, block, c->lds_bytes, s, pview, Q, c->lds_cfg, cur, (uint32_t) n_wg, c->d_next_pixel.p));
-                    MIW_TIMED(1, hipLaunchKernelGGL(k_sort_hits, grid, block, 0, s, pview, Q, cur, c->d_next_pixel.p));
-                    K.n_trace_closest++; K.n_trace_any++;
-                } else {
-                    if (!first) {
-                        MIW_TIMED(1, hipLaunchKernelGGL(k_trace<true>, grid, block, c->lds_bytes, s, c->view, Q, c->lds_cfg, cur));
-                        K.n_trace_any++;
-                    }
-                    MIW_TIMED(0, hipLaunchKernelGGL(k_trace<false>, grid, block, c->lds_bytes, s, c->view, Q, c->lds_cfg, cur));
-                    K.n_trace_closest++;
-                }
-                const uint32_t count_active = it == check_every - 1 ? 1u : 0u;
-                if (film_mode == 1)
-                    MIW_TIMED(2, hipLaunchKernelGGL(k_shade<true>, grid, block, 0, s, P, pview, Q, (double *) nullptr, c->d_cnt.p, count_active, cur, nxt));
-                else
-                    MIW_TIMED(2, hipLaunchKernelGGL(k_shade<false>, grid, block, 0, s, P, pview, Q, c->d_accum.p, c->d_cnt.p, count_active, cur, nxt));
-                K.n_shade++; K.iterations++;
-                first = false;
-            }
-            HIP_TRY(c, hipGetLastError());
-            Counters sum;
-            mi_status rs = read_counters(sum);
-            if (rs != MI_OK) return rs;
-            T.drain();
-            // active_lanes accumulates over the counting launches: the last one's share is the delta
-            unsigned long long active_now = sum.active_lanes - active_prev;
-            active_prev = sum.active_lanes;
-            if (active_now == 0) break;
-            if (c->cancel.load()) { result = MI_ERR_CANCELLED; break; }
-            if (out_of_time()) { result = MI_ERR_CANCELLED; break; }
-        }
-    }
+    return MI_OK;
+}
 #endif
 
+mi_status mi_render(mi_ctx *c, const mi_render_cfg *cfg, void *film) {
+    if (!c || !cfg || !film) return MI_ERR_INVALID;
+    if (!c->have_bvh) return fail(c, MI_ERR_STATE, "mi_render: call mi_scene_upload and mi_bvh_build first");
+    RenderFrame F(c, cfg);
+    MI_TRY(render_options(c, cfg, F.ropt));
+    MI_TRY(frame_geometry(F));
+    MI_TRY(frame_queues(F));                                      // (with the film plan: sample log + ordered gather if the log fits, else float64 atomics)
+    const miw_pick::Facts facts = pick_facts(c, F.ropt);        // what the kernel-class rules read (kernel_pick.h)
+    RenderLds L;
+    MI_TRY(render_lds(F, facts, L));
+    counters_reset(F);
+    mi_status result = MI_OK;                                     // (MI_ERR_CANCELLED: the film is assembled from what ran)
+    FilmReplay replay;                                            // (filled before the path kernel when the replay is queued beside it)
+    if (F.n_lanes > 0 && F.plan == 2) MI_TRY(render_resident(F, facts, L, replay, result));
+#if !MIW_SPECTRAL
+    else if (F.n_lanes > 0) MI_TRY(render_wavefront(F, result));
+#endif
     // film assembly -> caller's buffer (device pointer, or staged through d_out for a host pointer)
-    { const mi_status fs = assemble_film(c, cfg, ropt, P, s, T, FP, n_tiles, bs, bs2_log2, blocks_x, blocks_y, film_n, film, result, c->replay_enqueued ? &replay : nullptr); c->replay_enqueued = false; if (fs != MI_OK) return fs; }
-#undef MIW_TIMED
-    K.ms_render = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    const mi_status fs = assemble_film(F, film, result, c->replay_enqueued ? &replay : nullptr);
+    c->replay_enqueued = false;
+    if (fs != MI_OK) return fs;
+    F.K.ms_render = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - F.wall0).count();
     if (result == MI_ERR_CANCELLED) c->error = "render cancelled";
     return result;
 }
