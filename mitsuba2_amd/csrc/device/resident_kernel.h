@@ -1,6 +1,7 @@
 #ifndef MIW_KERNEL
 #define MIW_KERNEL __global__           /* a kernel that is no template: miwave_class.hip, which includes this header into further objects of the library, keeps it out of them */
 #endif
+#include "../render_plan.h"             /* the job pool's cursor arithmetic (miw_plan::pool_*): plain functions the CPU tier checks */
 // Plan 2 (resident): k_init_pixels, the shared pixel queue and k_path_resident (path / direct integrators).
 // Part of the single translation unit csrc/miwave.hip (included there, in this order; not a stand-alone header).
 // ---- the resident plan -----------------------------------------------------------------
@@ -96,7 +97,7 @@ struct QueueWork {
     // slots, so throughput is what it was. Evaluated every 16th iteration (one wave-wide minimum of the lanes' sample counters).
     uint32_t ticks, quarter, tail_prio, sample_end_; uint32_t *prog;      // prog: this wavefront's word in LDS (the wave-wide minimum)
     __device__ __forceinline__ void tick(uint32_t sample_idx, bool has_pixel) {
-        if (Frame) return;
+        if (Frame) { refill(); return; }
         if (!tail_prio) { ++ticks; return; }
         // (called from divergent code: the lanes that just fetched a pixel are not here — so no cross-lane shuffles; the
         // counter of the first active lane decides, the minimum goes through one LDS atomic per lane)
@@ -136,14 +137,89 @@ struct QueueWork {
         const uint32_t r = spp - sample_idx;                                                        // samples still to do: a chunk ends where that is a power of two >= job_min
         return Jobs && (r & (r - 1u)) == 0u && r >= Q->job_min ? sample_idx : sample_end;         // (job_min = 2^31 without chunks; r = 0 at the pixel's end: sample_end decides)
     }
+    // ---- the job pool (frame twins only; pool = MIW_JOB_POOL, 0: off) ----
+    // Why: a refill serves one lane almost every time (the lanes end their jobs on different trips) and costs the whole wavefront two dependent round trips past the L2,
+    // the atomic's return and the state word's load. Neither is needed per job: the ids are handed out in order and the state words of consecutive ids are consecutive
+    // words of Q->st (the queue is chunk-major). So the wavefront draws `pool` ids at a time and reads their state and pixel words in the same visit, one word per
+    // lane, into its block of dynamic LDS (render_plan.h: pool_wave_bytes; wave_words() below); a refill takes the next id of the cursor and its words from there.
+    //   who draws: the lanes that are RUNNING, at the top of a trip (tick -> refill), when the cursor is empty — fetch_job runs in divergent code, where only the asking
+    //     lanes could load, one word after the other. Lanes that ask while the cursor is empty (the launch's start, a wavefront whose lanes all ask at once) draw for
+    //     themselves as before: nobody waits for a refill that no running lane would make.
+    //   a prefetched word is FINAL if its counter stands at the chunk's first sample (nobody writes that slot again until this job ends: the single-copy assumption the
+    //     direct load makes too) or if it says LF_DONE (never taken back). Otherwise the chunk before had not landed when the batch was drawn: the lane takes
+    //     today's path — the direct sc1 load, parking in job_pend, asking again next trip.
+    //   progress: a pool may hold ids no lane has started. Take the smallest unstarted id. If it is parked at a lane, its predecessor has a smaller id, has therefore
+    //     started, and will finish. If it is in a wavefront's pool, every lane of that wavefront is running or exhausted or parked; a parked lane would hold an unstarted
+    //     id taken earlier — from the cursor, which hands out ascending ids, or drawn by itself, which happens only while the cursor is empty, before this batch was
+    //     drawn — hence smaller: a contradiction. A lane is exhausted only by an id >= job_total, from the cursor (then no valid id is left behind it) or drawn while the
+    //     cursor was empty; and a batch is drawn by running lanes, which will ask. So a lane of the wavefront is running and will take the id.
+    //   hoarding at the queue's end: a wavefront holds at most `pool` unstarted ids while lanes elsewhere find the queue empty; its 64 lanes take them as their
+    //     jobs end, so the launch ends at most pool / 64 of one smallest job's duration later than without the pool.
+    // this wavefront's block: [next, end][pool, -][segments][samples][shadow rays][-, -][ring: 32 x 16 B state][32 x 4 B pixel]. A twin is launched with ONE size of dynamic
+    // LDS whatever the scene (render_plan.h: MIW_TWIN_LDS) and the blocks stand at its end, so a block's address is a constant plus the wavefront's number times a
+    // constant: worked out from threadIdx.x where it is used, no register kept for it through the pixel loop. The ring has MIW_POOL_MAX slots whatever the pool:
+    // a batch is at most that many consecutive ids, so slot id & (MIW_POOL_MAX - 1) is one id's alone until the next batch is drawn.
+    __device__ __forceinline__ uint32_t pool_size() const { return (uint32_t) __builtin_amdgcn_readfirstlane((int) lds_get(wave_words() + 2)); }
+    __device__ __forceinline__ static uint32_t *wave_words() { extern __shared__ uint4 smem_pool[]; return reinterpret_cast<uint32_t *>(smem_pool) + MIW_POOL_AT / 4u + (threadIdx.x >> 6) * (MIW_POOL_STRIDE / 4u); }
+    __device__ __forceinline__ static uint32_t *ring_state(uint32_t id) { return wave_words() + MIW_POOL_HEAD / 4u + 4u * miw_plan::pool_ring_slot(id, MIW_POOL_MAX); }
+    __device__ __forceinline__ static uint32_t *ring_pixel(uint32_t id) { return wave_words() + MIW_POOL_HEAD / 4u + 4u * MIW_POOL_MAX + miw_plan::pool_ring_slot(id, MIW_POOL_MAX); }
+    __device__ __forceinline__ static uint32_t lds_get(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }   // (words other lanes of the wavefront write: never kept in a register across trips)
+    __device__ __forceinline__ static void lds_set(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+    __device__ __forceinline__ void init_pool(uint32_t pool_) {
+        uint32_t *wv = wave_words();
+        if ((threadIdx.x & 63u) < MIW_POOL_HEAD / 4u) lds_set(wv + (threadIdx.x & 63u), (threadIdx.x & 63u) == 2u ? pool_ : 0u);   // cursor empty, counters 0 (read and written by this wavefront alone: no barrier)
+    }
+    __device__ __forceinline__ uint32_t chunk_first(uint32_t j) const { return j ? spp - (Q->job_pow >> (j - 1u)) : 0u; }   // the sample chunk j of a pixel starts at
+    __device__ __forceinline__ static U4v load_state(const U4 *p) {
+        U4v w;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(p) : "memory");
+#endif
+        return w;
+    }
+    // called by the running lanes at the top of every trip: draw a batch when the cursor is empty
+    __device__ __forceinline__ void refill() {
+        const uint32_t pool = pool_size();
+        if (!pool) return;                                      // (wave-uniform)
+        uint32_t *wv = wave_words();
+        miw_plan::JobCursor cur{ (uint32_t) __builtin_amdgcn_readfirstlane((int) lds_get(wv)), (uint32_t) __builtin_amdgcn_readfirstlane((int) lds_get(wv + 1)) };
+        if (!miw_plan::pool_empty(cur) || miw_plan::pool_dry(cur)) return;
+        const unsigned long long m = __ballot(1);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u)), n_run = (uint32_t) __popcll(m);
+        uint32_t base = 0;
+        if (rank == 0u) base = atomicAdd(next_pixel, pool);
+        base = (uint32_t) __builtin_amdgcn_readfirstlane((int) base);     // (the first active lane is the one of rank 0)
+        cur = miw_plan::pool_batch(base, pool, Q->job_total);
+        if (!miw_plan::pool_dry(cur)) for (uint32_t id = base + rank; id < cur.end; id += n_run) {   // one word per lane: a single pass once `pool` lanes run
+            const uint32_t j = id / n_lanes, slot = id - j * n_lanes;
+            const uint32_t px = Q->pixel[slot];
+            const U4v w = load_state(Q->st + slot);
+            uint32_t *e = ring_state(id);
+            lds_set(e, w.x); lds_set(e + 1, w.y); lds_set(e + 2, w.z); lds_set(e + 3, w.w);
+            lds_set(ring_pixel(id), px);
+        }
+        if (rank == 0u) { lds_set(wv, cur.next); lds_set(wv + 1, cur.end); }
+    }
     __device__ __forceinline__ bool fetch_job(uint32_t &pixel, U4 &st) {
         for (;;) {
             const uint32_t parked = job_pend();
             if (parked == 0xffffffffu) return false;
             uint32_t id = parked - 1u;
             const bool fresh = parked == 0u;
-            const unsigned long long b = __ballot(fresh);
-            if (fresh) {
+            bool draw = fresh, pooled = false;                  // draw: this lane asks the queue itself; pooled: its id and words come from the wavefront's pool
+            if constexpr (Frame) {                              // (straight-line: the lanes that do not ask read along. Without a pool — MIW_JOB_POOL=0 — refill never draws,
+                                                                // the cursor stays empty as init_pool left it, and every lane draws for itself)
+                const unsigned long long a = __ballot(fresh);
+                uint32_t *wv = wave_words();
+                const miw_plan::JobCursor cur{ lds_get(wv), lds_get(wv + 1) };                      // (every lane reads the same two words)
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t) (a >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) a, 0u)), asking = (uint32_t) __popcll(a);
+                if (fresh && rank == 0u) lds_set(wv, miw_plan::pool_after(cur, asking).next);
+                if (fresh && miw_plan::pool_dry(cur)) { job_pend() = 0xffffffffu; return false; }
+                pooled = fresh && rank < miw_plan::pool_take(cur, asking);
+                id = pooled ? cur.next + rank : id; draw = fresh && !pooled;
+            }
+            const unsigned long long b = __ballot(draw);
+            if (draw) {
                 const uint32_t me = threadIdx.x & 63u, leader = (uint32_t) __ffsll((long long) b) - 1u;
                 uint32_t base = 0;
                 if (me == leader) base = atomicAdd(next_pixel, (uint32_t) __popcll(b));
@@ -152,13 +228,18 @@ struct QueueWork {
                 if (id >= Q->job_total) { job_pend() = 0xffffffffu; return false; }
             }
             const uint32_t j = id / n_lanes, slot = id - j * n_lanes;
-            const uint32_t px = Q->pixel[slot];
+            uint32_t px = 0;
             U4v w;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(w) : "v"(Q->st + slot) : "memory");
-#endif
+            bool have = false;
+            if (Frame && pooled) {                              // the words read when the batch was drawn
+                const uint32_t *e = ring_state(id);
+                w.x = lds_get(e); w.y = lds_get(e + 1); w.z = lds_get(e + 2); w.w = lds_get(e + 3);
+                px = lds_get(ring_pixel(id));
+                have = (w.z & LF_DONE) || w.w == chunk_first(j);
+            }
+            if (!have) { px = Q->pixel[slot]; w = load_state(Q->st + slot); }
             if (w.z & LF_DONE) { job_pend() = 0u; continue; }                     // pixel outside its clipped block, or already complete
-            if (w.w != (j ? spp - (Q->job_pow >> (j - 1u)) : 0u)) { job_pend() = id + 1u; return false; }   // the chunk before is still running: ask again
+            if (w.w != chunk_first(j)) { job_pend() = id + 1u; return false; }   // the chunk before is still running: ask again
             job_pend() = 0u;
             lane = slot; pixel = px;
             st.x = w.x; st.y = w.y; st.z = w.z; st.w = w.w;
@@ -249,6 +330,30 @@ struct QueueWork {
     }
 };
 
+// The frame twin's counters (path.h: path_step's `Cnt`): per wavefront ONE 64-bit word each in its block of dynamic LDS (render_plan.h: pool_wave_bytes) instead of three
+// registers per lane. An increment adds the population count of the lanes that reach it, through the first of them; the totals are the lanes' sums to the unit, and the
+// end-of-kernel wave_sum falls away. (Every lane adding 1 to the word instead — 64 adds to one LDS address, three times per segment — ran the C2 frame 3 ms slower than
+// the counters in registers: profiles/r12_job_pool.txt.)
+template <uint32_t K> struct WaveCount {                       // words K, K + 1 of the block (QueueWork::wave_words: the wavefront's number times a constant, no register of its own)
+    __device__ __forceinline__ static uint32_t *block() { extern __shared__ uint4 smem_cnt[]; return reinterpret_cast<uint32_t *>(smem_cnt) + MIW_POOL_AT / 4u + (threadIdx.x >> 6) * (MIW_POOL_STRIDE / 4u); }
+    __device__ __forceinline__ static unsigned long long *word() { return reinterpret_cast<unsigned long long *>(block() + K); }
+    __device__ __forceinline__ void operator++(int) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the population count of the lanes here, added by the first of them: the execution mask narrowed to that lane around the add and put back, in one statement
+        // (so the compiler never sees the narrowed mask: between the statement's first and last instruction nothing of its own runs, and a volatile asm is neither
+        // duplicated nor moved into other control flow). The address operand is the low half of the generic pointer: on gfx9 the LDS aperture's base has its low
+        // 32 bits clear, so that half IS the byte offset in LDS, which ds_add takes.
+        unsigned long long keep, sum;
+        asm volatile("s_mov_b64 %0, exec\n\ts_bcnt1_i32_b64 vcc_lo, exec\n\ts_ff1_i32_b64 vcc_hi, exec\n\ts_lshl_b64 exec, 1, vcc_hi\n\ts_mov_b32 vcc_hi, 0\n\t"
+                     "v_mov_b64 %1, vcc\n\tds_add_u64 %2, %1 offset:%3\n\ts_mov_b64 exec, %0"
+                     : "=&s"(keep), "=&v"(sum) : "v"((uint32_t) (uintptr_t) block()), "n"(4u * K) : "memory", "scc", "vcc");
+#endif
+    }
+    __device__ __forceinline__ unsigned long long get() const { return __hip_atomic_load(word(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+};
+static_assert(MIW_BLOCK / 64u * MIW_POOL_STRIDE == MIW_POOL_FRONT, "a block per wavefront of the workgroup, found by threadIdx.x >> 6");
+struct WaveCounters { WaveCount<4u> segments; WaveCount<6u> samples; WaveCount<8u> shadow_rays; };
+
 #ifndef MIW_DIRECT_WAVES
 /* Waves per SIMD the direct-integrator kernels are compiled for. At 2 (256 VGPRs) none of them spills, at 3 (168) they keep
    16 - 108 registers in scratch (60 / 216 in the MATS_ALL ones when this was measured) — and are faster all the same (path kernel of one frame,
@@ -327,6 +432,12 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
             __shared__ uint32_t s_prog[MIW_BLOCK / 64];
             if (cfg.tail_prio) work.enable_tail_prio(sample_end, &s_prog[threadIdx.x >> 6]);
         }
+        if constexpr (Frame) {
+            // the twin's launch says the job pool in an argument of the film tile, which no sample-log launch reads: T.side (miwave.hip: launch_path_kernel)
+            work.init_pool(T.side);
+            const WaveCounters wave{};
+            pixel_stream_render<Mats, Analytic, Frames, Feat & FEAT_ALL>(P, sc, sample_end, work, tr2, &wave);
+        } else
         if constexpr (Integ == INTEG_DIRECT) pixel_stream_render_direct<Mats, Analytic>(P, sc, sample_end, work, tr2, &local);
         else pixel_stream_render<Mats, Analytic, Frames, Feat & FEAT_ALL>(P, sc, sample_end, work, tr2, &local);
     } else if (lane < P.n_lanes) {
@@ -356,7 +467,10 @@ __global__ __launch_bounds__(MIW_BLOCK, Waves ? Waves : Integ == INTEG_DIRECT ? 
             unsafeAtomicAdd(accum + ((size_t) fy * P.film.crop_w + fx) * MIW_FILM_CHANNELS + k, v);
         }
     }
-    unsigned long long a = wave_sum(local.segments), b = wave_sum(local.samples), c = wave_sum(local.shadow_rays);
+    unsigned long long a, b, c;
+    if constexpr (Frame) {
+        a = WaveCount<4u>{}.get(); b = WaveCount<6u>{}.get(); c = WaveCount<8u>{}.get();
+    } else { a = wave_sum(local.segments); b = wave_sum(local.samples); c = wave_sum(local.shadow_rays); }
     if ((threadIdx.x & 63) == 0) {
         Counters *shard = cnt + ((blockIdx.x * (MIW_BLOCK / 64) + (threadIdx.x >> 6)) & (MIW_CNT_SHARDS - 1));
         if (a) atomicAdd(&shard->segments, a);

@@ -184,6 +184,7 @@ static const KnobInfo g_knobs[] = {
     { "MIW_JOB_CHUNK_FORCE", "1: chunk jobs whatever the frame's size (tests of the hand-over between lanes)" },
     { "MIW_LEAN", "0: a packet scene without environment map and vertex normals, rendered without the moment integrator, keeps the full path kernel instead of its lean twin (kernel_pick.h: packet_features)" },
     { "MIW_FRAME_TWIN", "0: a full frame of chunk jobs keeps the lean twin of its packet path kernel instead of the frame twin, which has the facts of such a launch compiled in (kernel_pick.h: frame_twin)" },
+    { "MIW_JOB_POOL", "chunk-job ids a wavefront of a frame twin draws from the queue at a time, their state words read into its LDS block with the draw (a power of two from 2 to 32; default 32); 0: every job drawn on its own (resident_kernel.h: QueueWork::refill)" },
     { "MIW_PACKET_SHARD4", "0: a plain-diffuse packet job of at most four wavefronts of pixels per SIMD keeps the five-wavefront (96-register) kernel" },
     { "MIW_PLACE_MEASURE", "divisor: the measuring launch runs spp / divisor samples" },
     { "MIW_PLACE_SPREAD", "0 | 1: placed pieces = consecutive sorted lanes | one lane of every cost stratum" },
@@ -2187,6 +2188,7 @@ struct PathRoute {
     bool place; uint32_t measure_end, n_pieces;                   // measuring + placed launch; the measuring launch's samples; 64-lane pieces
     int overlap_mode; bool overlap;                               // the film replay beside the render (MIW_FILM_OVERLAP)
     bool pooled;                                                  // k_path_pooled
+    bool twin_fits; uint32_t job_pool; size_t twin_rlds;   // a frame twin's launch: the render's layout ends before its blocks and no resident workgroup is lost; MIW_JOB_POOL as launched; its dynamic LDS
 };
 static mi_status path_route(RenderFrame &F, const miw_pick::Facts &facts, const RenderLds &L, PathRoute &R) {
     mi_ctx *c = F.c; const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; const FilmPlan &FP = F.FP;
@@ -2225,6 +2227,17 @@ static mi_status path_route(RenderFrame &F, const miw_pick::Facts &facts, const 
     // ... of which a packet kernel keeps resident only the workgroups whose LDS — packets, boxes, thresholds, tables, its static 1 KB — a CU holds:
     // the grid, the placement and the replay's room below count what IS resident, not what the registers alone would allow
     const uint32_t res_waves = tiny && film_mode == 1 ? std::max(1u, std::min(res_waves_compiled, miw_plan::lds_workgroups(rlds))) : res_waves_compiled;
+    // A frame twin (kernel_pick.h: frame_twin, chosen at the launch) keeps a block per wavefront in dynamic LDS: the cursor and ring of its job pool (MIW_JOB_POOL ids
+    // drawn at a time, their state words read with the draw: resident_kernel.h) and the launch's three counters. It is launched with ONE size of dynamic LDS, the
+    // blocks at its end (render_plan.h: MIW_TWIN_LDS, MIW_POOL_AT). That must not cost a resident workgroup, and this layout must end before the blocks: a launch
+    // where either fails keeps the lean twin. 32: profiles/r12_job_pool.txt.
+    // (Not the bytes the pool needs, counted into this layout: a block whose place depends on the scene or on the pool needs a register for its address through the
+    // pixel loop, and the twin has none — every such form spilled past the bounds of tests/test_job_pool_kernel_budget.py. The fixed size is well inside a fifth of a
+    // CU, so no launch loses a workgroup to it. MIW_JOB_POOL=0 takes the same launch: no batch is ever drawn and every job is drawn on its own, but fetch_job still
+    // reads the (empty) cursor and the counters are the per-wavefront ones — it is the twin without batches, about 1 ms slower on C2 than the kernel before the pool.)
+    R.job_pool = miw_plan::pool_size(ropt.num("MIW_JOB_POOL", 32));
+    R.twin_fits = tiny && film_mode == 1 && rlds <= MIW_POOL_AT && std::min(res_waves_compiled, miw_plan::lds_workgroups(MIW_TWIN_LDS)) >= res_waves;
+    R.twin_rlds = MIW_TWIN_LDS;
     bool place = film_mode == 1 && !direct && (tiny || phased_placeable) && miw_plan::place_window(n_lanes, res_waves, n_simd) &&
                  cfg->spp >= 128u && per_launch >= cfg->spp && cfg->timeout_s <= 0.f;
     if (ropt.off("MIW_PLACE")) place = false;
@@ -2338,8 +2351,12 @@ static mi_status place_statistics(RenderFrame &F, const PathRoute &R, bool place
     return MI_OK;
 }
 
+// the rule of the frame twins with the library's switch, asked where the chunks are cut and where the kernel is launched
+static bool takes_frame_twin(const Options &ropt, const miw_pick::Pick &pick, bool direct, uint32_t feat, const miw_pick::LaunchFacts &lf) {
+    return miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
+}
 // ---- mi_render, resident plan, phase "chunk jobs": LaneQueues::job_* and mi_counters::job_chunk* of the launch that begins at sample `done` ----
-static void chunk_jobs(RenderFrame &F, const PathRoute &R, const RenderLds &L, uint32_t done) {
+static void chunk_jobs(RenderFrame &F, const miw_pick::Facts &facts, const PathRoute &R, const RenderLds &L, uint32_t done) {
     const mi_render_cfg *cfg = F.cfg; const Options &ropt = F.ropt; LaneQueues &Q = F.Q; mi_counters &K = F.K; const uint32_t n_lanes = F.n_lanes;
     const bool tiny = R.tiny, phased = R.phased, place = R.place, overlap = R.overlap, pooled_fits = L.pooled_fits;
     const uint32_t per_launch = R.per_launch, res_waves = R.res_waves, n_simd = R.n_simd;
@@ -2353,6 +2370,16 @@ static void chunk_jobs(RenderFrame &F, const PathRoute &R, const RenderLds &L, u
     // per pixel instead of eight, the tail as long as the smallest. The phase machine's full frames (C3, C4) take the same queue.
     if ((tiny || (phased && MIW_PHASED_JOBS != 0)) && !pooled_fits && !place && !overlap && done == 0 && per_launch >= cfg->spp && cfg->timeout_s <= 0.f) {
         uint32_t jmin = tiny ? 64u : 32u;                                 // (gpurun r6s, halving chunks: C2 4 461 / 4 316 / 4 389 Msamples/s at 64 / 32 / 128; C3 1 298 / 1 305, C4 522 / 528 at 64 / 32)
+        // A frame twin with its job pool draws `pool` jobs per atomic, so the queue's counter no longer bounds the chunk: 16 (C2, pool 32: path kernel 192.94 - 193.01 ms
+        // at 16, 193.42 - 193.46 at 32, 195.41 - 195.46 at 64, the parent's 195.18 - 195.46: profiles/r12_job_pool.txt, visit 3). Asked of the rule the launch asks (kernel_pick.h: frame_twin), with the facts
+        // that launch will have: chunk jobs, one queue and no group counts by the condition above, no tail priorities unless MIW_TAIL_PRIO turns them on.
+        // (only a frame that takes chunk jobs for its own size: one that has them forced — MIW_JOB_CHUNK_FORCE, the tests of the hand-over — keeps 64)
+        if (tiny && R.twin_fits && R.job_pool && miw_plan::chunks_enough(n_lanes, res_waves, n_simd)) {
+            miw_pick::LaunchFacts lf;
+            lf.job_chunks = true; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = true; lf.tail_prio = ropt.on("MIW_TAIL_PRIO");
+            lf.leaf_filter = F.c->lds_cfg.leaves != 0u; lf.group_counts = false;
+            if (takes_frame_twin(ropt, miw_pick::resident_path(facts, false), R.direct, R.feat, lf)) jmin = 16u;
+        }
         if (const char *e = ropt.get("MIW_JOB_CHUNK")) jmin = (uint32_t) std::max(0, atoi(e));   // (a value that is no power of two: off — render_plan.h: chunk_schedule)
         // from 1.2 pixels per resident lane on (render_plan.h: chunks_enough)
         bool enough = miw_plan::chunks_enough(n_lanes, res_waves, n_simd);
@@ -2507,8 +2534,10 @@ static mi_status launch_path_kernel(RenderFrame &F, const miw_pick::Facts &facts
             miw_pick::LaunchFacts lf;
             lf.job_chunks = Q.job_chunk != 0u; lf.log_rec16 = Q.log_rec != nullptr; lf.one_queue = rcfg.queues == 1u; lf.tail_prio = rcfg.tail_prio != 0u;
             lf.leaf_filter = c->lds_cfg.leaves != 0u; lf.group_counts = Q.group_done != nullptr;
-            const bool frame = miw_pick::frame_twin(pick, direct, feat, lf, !ropt.off("MIW_FRAME_TWIN"));
-#define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
+            const bool frame = R.twin_fits && takes_frame_twin(ropt, pick, direct, feat, lf);
+            // (the twin's job pool — path_route — goes in the film tile's arguments, which a sample-log launch does not read)
+            TileArgs TW = TA; TW.side = R.job_pool;
+#define MIW_FRAME_LAUNCH(T, M) if (frame && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; frame_launched = true; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_FRAME>), pgrid, block, R.twin_rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TW, c->d_next_pixel.p)); } else
             MIW_LEAN_LIST(MIW_FRAME_LAUNCH)
 #undef MIW_FRAME_LAUNCH
 #define MIW_LEAN_LAUNCH(T, M) if (feat == FEAT_NONE && !direct && MIW_PICKED(T, M, false)) { feat_launched = FEAT_NONE; MIW_TIMED(6, MIW_LAUNCH_NAMED(ropt, (k_path_resident<true, T, M, false, INTEG_PATH, false, 0, FEAT_NONE>), pgrid, block, rlds, s, P, c->view, Q, (double *) nullptr, c->d_cnt.p, rcfg, end, TA, c->d_next_pixel.p)); } else
@@ -2559,7 +2588,7 @@ static mi_status render_resident(RenderFrame &F, const miw_pick::Facts &facts, c
                 MI_TRY(overlap_prepare(F));
                 if (Q.group_done) HIP_TRY(c, hipEventRecord(c->ev_fork, s));
             }
-            chunk_jobs(F, R, L, done);
+            chunk_jobs(F, facts, R, L, done);
             if (R.place && done == 0) { PK.end = R.measure_end; Q.lane_cost = c->d_lane_cost.p; Q.simd_ids = c->d_simd_ids.p; }   // the measuring launch
             else if (R.place) MI_TRY(place_deal(F, R, place_tmp_bytes, PK.rcfg, place_stats_due));                               // the placed launch
         }
@@ -2572,7 +2601,8 @@ static mi_status render_resident(RenderFrame &F, const miw_pick::Facts &facts, c
         // which instantiation this launch was, said after the launch site set it: 0x0 only where a lean twin (FEAT_NONE) was launched — not for a class without
         // a twin, the overlap's Groups = true pair, the direct integrator or the float64-atomics film, which run the full kernel whatever mask was chosen
         if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased) fprintf(stderr, "[miwave] packet path kernel launched: scene features 0x%x of 0x%x compiled in (mask chosen for the render: 0x%x)\n", PK.feat_launched, (uint32_t) FEAT_ALL, R.feat);
-        if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased) fprintf(stderr, "[miwave] packet path kernel launched: frame twin %s\n", PK.frame_launched ? "yes (chunk jobs, one queue, 16-byte log, no tail priorities, leaf filter compiled in)" : "no");
+        if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased && !PK.frame_launched) fprintf(stderr, "[miwave] packet path kernel launched: frame twin no\n");
+        if (ropt.get("MIW_DEBUG") && R.tiny && !R.phased && PK.frame_launched) fprintf(stderr, "[miwave] packet path kernel launched: frame twin yes (chunk jobs, one queue, 16-byte log, no tail priorities, leaf filter compiled in), job pool %u, smallest chunk %u, %zu bytes of LDS per workgroup\n", R.job_pool, Q.job_min, R.twin_rlds);
         K.n_path++; K.iterations++;
         done = PK.end;
         // cancel() / timeout take effect at launch granularity (the reference checks should_stop() per block)

@@ -31,6 +31,37 @@ inline ChunkSchedule chunk_schedule(uint32_t spp, uint32_t jmin) {
 // 6 ranks = 1.06: 54.9 / 54.6; at about ONE pixel per lane every pixel is in flight all the time and no lane finds a second job: 8 ranks 47.1 against the placed launches' 41.4)
 inline bool chunks_enough(uint32_t n_lanes, uint32_t res_waves, uint32_t n_simd) { return (uint64_t) n_lanes * 5u >= (uint64_t) 6u * 64u * res_waves * n_simd; }
 
+// ---- the job pool of a frame twin's wavefront (device/resident_kernel.h: QueueWork<..., Frame>::refill / fetch_job) ----
+// A wavefront draws `pool` consecutive ids from the queue at a time and keeps the half-open range [next, end) of those nobody has taken yet; the state word
+// and the pixel word of id sit in ring slot id & (pool - 1) of its LDS block, read when the batch was drawn. The device calls these very functions.
+struct JobCursor { uint32_t next, end; };
+#define MIW_POOL_DRY 0xffffffffu                     /* next == end == MIW_POOL_DRY: a batch began at or past job_total — the queue is empty for good, no further draw */
+// MIW_JOB_POOL as given -> the pool: a power of two from 2 to 32 (a lane reads one word of a batch; MIW_POOL_MAX below), anything else is 0 = every job drawn on its own
+constexpr uint32_t pool_size(int given) { return given >= 2 && given <= 32 && (given & (given - 1)) == 0 ? (uint32_t) given : 0u; }
+// the cursor after a draw that returned `base`: ids at or above job_total are dropped
+constexpr JobCursor pool_batch(uint32_t base, uint32_t pool, uint32_t job_total) {
+    return base >= job_total ? JobCursor{ MIW_POOL_DRY, MIW_POOL_DRY } : JobCursor{ base, job_total - base < pool ? job_total : base + pool };
+}
+constexpr bool pool_dry(JobCursor c) { return c.next == MIW_POOL_DRY; }
+constexpr bool pool_empty(JobCursor c) { return c.next == c.end; }                      // (a dry pool is empty too: test pool_dry first)
+// `asking` lanes ask at once, ranked 0 .. asking - 1: the first pool_take() of them get id next + rank, the cursor moves past those; the others draw for themselves
+constexpr uint32_t pool_take(JobCursor c, uint32_t asking) { return pool_dry(c) ? 0u : (c.end - c.next < asking ? c.end - c.next : asking); }
+constexpr JobCursor pool_after(JobCursor c, uint32_t asking) { return JobCursor{ c.next + pool_take(c, asking), c.end }; }
+constexpr uint32_t pool_ring_slot(uint32_t id, uint32_t pool) { return id & (pool - 1u); }
+// a wavefront's block in the dynamic LDS behind the render's layout: cursor (8 B), the pool's size (4 B of 8), the three counters of the launch (3 x 8 B), 8 B spare, `pool` state words (16 B), `pool` pixel words
+#define MIW_POOL_HEAD 48u
+constexpr uint32_t pool_wave_bytes(uint32_t pool) { return MIW_POOL_HEAD + 20u * pool; }
+constexpr uint32_t pool_lds_bytes(uint32_t pool, uint32_t waves_per_workgroup) { return waves_per_workgroup * pool_wave_bytes(pool); }
+// A frame twin is launched with ONE size of dynamic LDS whatever the scene, the most that still lets a CU hold five workgroups, and the blocks stand at its end at the
+// stride of the largest pool: a wavefront finds its block from its number alone (no register holds the address through the pixel loop: the twin has none to spare,
+// tests/test_job_pool_kernel_budget.py). A scene whose own layout reaches into the blocks keeps the lean twin (miwave.hip: path_route).
+#define MIW_POOL_MAX 32u
+#define MIW_POOL_STRIDE 688u                         /* pool_wave_bytes(MIW_POOL_MAX) */
+#define MIW_POOL_FRONT 2752u                         /* pool_lds_bytes(MIW_POOL_MAX, 4 wavefronts of a workgroup): a multiple of 16 */
+#define MIW_TWIN_LDS 26624u                          /* 26 KB: with the static 1 040 well inside a fifth of a CU (32 KB) whatever granule the LDS is handed out in */
+#define MIW_POOL_AT (MIW_TWIN_LDS - MIW_POOL_FRONT)  /* where the blocks begin */
+static_assert(pool_wave_bytes(MIW_POOL_MAX) == MIW_POOL_STRIDE && pool_lds_bytes(MIW_POOL_MAX, 4u) == MIW_POOL_FRONT && MIW_POOL_FRONT % 16u == 0u && MIW_TWIN_LDS % 16u == 0u, "the twin's blocks");
+
 // ---- placed queues: the pieces of 64 sorted lanes dealt to `nqueues` SIMD queues of `slots` pieces each ----
 // The pieces arrive in descending cost (they are cuts of the sorted lane list), so "longest piece first onto the emptiest queue" is dealt
 // in rounds, alternating direction (round 0: piece i to queue i; round 1: piece N + i to queue N - 1 - i; ...): every queue gets one
@@ -49,6 +80,9 @@ inline uint32_t deal_pieces(uint32_t n_pieces, uint32_t nqueues, uint32_t slots,
 }
 
 // workgroups of a kernel with `dyn` bytes of dynamic LDS (+ its static __shared__, in granules) that one CU holds
+// KNOWN ERROR at the edge: the part hands LDS out in larger granules than MIW_LDS_GRANULE. A launch of 31 232 dynamic bytes, five workgroups per CU by this count,
+// ran with four (profiles/r12_job_pool.txt, visit 2). Every launch sized by it so far asks for what its scene needs, far from a boundary; a size chosen to sit AT a
+// boundary must keep a margin (MIW_TWIN_LDS does: 26 KB where 31 KB counts as five). The true granule has not been measured.
 inline uint32_t lds_workgroups(size_t dyn) {
     const size_t per = (dyn + MIW_LDS_STATIC + 16u + MIW_LDS_GRANULE - 1u) / MIW_LDS_GRANULE * MIW_LDS_GRANULE;
     return (uint32_t) (MIW_LDS_PER_CU / per);
