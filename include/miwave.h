@@ -512,6 +512,37 @@ typedef struct {
 int32_t   mi_aov_channel_count(const mi_aov_cfg *aov);
 mi_status mi_render_aov(mi_ctx *ctx, const mi_render_cfg *cfg, const mi_aov_cfg *aov, void *film);
 
+/* The general sensor route: SamplingIntegrator::render for a sensor the resident path kernels do not know. mi_render's kernels
+ * draw the perspective camera's three numbers per sample; a sensor with another draw ledger (integrator.cpp:242-252) — thinlens
+ * (src/sensors/thinlens.cpp) inserts a next_2d for the aperture, a positive shutter time a next_1d — is rendered here, a frame
+ * advancing one sample per round: a camera kernel, then mi_sample's launch for device-resident rays, then the film replayed in
+ * ImageBlock::put's float32 order (the five channels X Y Z A W of mi_render's film).
+ *   MI_SENSOR_PERSPECTIVE  the camera of mi_render_cfg as it stands: the same frame as mi_render's, word for word, through this route
+ *   MI_SENSOR_THINLENS     the same projective state (no principal point offset) with aperture_radius and focus_distance
+ * mi_render_sensor reads of cfg: the camera matrices and clips; the film, filter, block and seed fields; spp; integrator, max_depth,
+ * rr_depth, emitter_samples, bsdf_samples, hide_emitters (the child's parameters, as mi_sample takes them); accumulate,
+ * film_on_device, timeout_s, profile (times into ms_path — of which ms_init is the camera kernel's —, ms_film_blocks, ms_film_merge,
+ * ms_render; samples is set). It refuses with MI_ERR_INVALID and a message that names the field: tile_list (shards), film_f64,
+ * film_mode == 2, plan == 1, moment_pass != 0, an unknown struct_size or type, a non-finite or non-positive lens parameter.
+ * mi_cancel() and timeout_s end it between rounds (MI_ERR_CANCELLED). */
+enum { MI_SENSOR_PERSPECTIVE = 0, MI_SENSOR_THINLENS = 1 };
+typedef struct {
+    uint32_t struct_size;            /* sizeof(mi_sensor_desc) of the caller: the library refuses a size it does not know      */
+    int32_t  type;                   /* MI_SENSOR_*                                                                          */
+    float    aperture_radius;        /* thinlens: > 0                                                                        */
+    float    focus_distance;         /* thinlens: > 0                                                                        */
+    float    shutter_open, shutter_open_time;   /* open_time > 0: one next_1d per sample (integrator.cpp:248-250)             */
+    uint32_t debug_group_tiles;      /* 0: the library sizes the tile groups; else that many tiles per group (tests)         */
+} mi_sensor_desc;                    /* 7 words */
+mi_status mi_render_sensor(mi_ctx *ctx, const mi_render_cfg *cfg, const mi_sensor_desc *sensor, void *film);
+/* Sensor::sample_ray for n samples (no differentials). Needs a context and no scene. position_sample: 2 n floats, already divided
+ * by the crop size; aperture_sample: 2 n floats or NULL = (.5, .5); wavelength_sample: n floats (scalar_spectral library), else
+ * NULL. rays: eight arrays of n floats; wavelengths: 4 n floats and weights: N n floats (N = mi_spectrum_channels()), or NULL.
+ * on_device != 0: every array is device memory. Reads of cfg the camera matrices, clips and principal point offset only. */
+mi_status mi_sensor_sample_ray(mi_ctx *ctx, const mi_render_cfg *cfg, const mi_sensor_desc *sensor,
+                               const float *position_sample, const float *aperture_sample, const float *wavelength_sample,
+                               const mi_rays_soa *rays, float *wavelengths, float *weights, uint64_t n, int32_t on_device);
+
 /* Integrator::cancel() — may be called from another thread */
 mi_status mi_cancel(mi_ctx *ctx);
 

@@ -149,7 +149,13 @@ class mi_aov_cfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_types", C.c_uint32), ("types", C.c_uint8 * 32), ("nested", C.c_int32), ("child", mi_sample_cfg)]
 
 
+class mi_sensor_desc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("type", C.c_int32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float),
+                ("shutter_open", C.c_float), ("shutter_open_time", C.c_float), ("debug_group_tiles", C.c_uint32)]
+
+
 MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
+MI_SENSOR_PERSPECTIVE, MI_SENSOR_THINLENS = 0, 1
 # mi_aov_cfg::types in the order of aov.cpp's grammar, and mi_aov_cfg::nested
 MI_AOV = dict(depth=0, position=1, uv=2, geo_normal=3, sh_normal=4, dp_du=5, dp_dv=6, duv_dx=7, duv_dy=8)
 MI_AOV_CHANNELS = dict(depth=1, position=3, uv=2, geo_normal=3, sh_normal=3, dp_du=3, dp_dv=3, duv_dx=2, duv_dy=2)
@@ -172,7 +178,7 @@ MI_SYMBOLS = ["mi_spectrum_channels", "mi_device_count", "mi_create", "mi_destro
               "mi_ray_intersect", "mi_sample_emitter_direction", "mi_pdf_emitter_direction", "mi_emitter_eval", "mi_sample",
               "mi_film_alloc", "mi_film_free", "mi_film_download", "mi_film_reduce",
               "mi_set_option", "mi_get_option", "mi_option_count", "mi_option_name", "mi_option_help",
-              "mi_render_aov", "mi_aov_channel_count"]
+              "mi_render_aov", "mi_aov_channel_count", "mi_render_sensor", "mi_sensor_sample_ray"]
 
 
 VARIANT_SUFFIX = {"scalar_rgb": "", "scalar_spectral": "_spectral"}
@@ -233,6 +239,10 @@ def load_device_lib(variant="scalar_rgb"):
     lib.mi_sample.argtypes = [vp, C.POINTER(mi_sample_cfg), C.POINTER(mi_rays_soa), vp, vp, vp, vp, vp, C.c_uint64]; lib.mi_sample.restype = C.c_int32
     lib.mi_render_aov.argtypes = [vp, C.POINTER(mi_render_cfg), C.POINTER(mi_aov_cfg), vp]; lib.mi_render_aov.restype = C.c_int32
     lib.mi_aov_channel_count.argtypes = [C.POINTER(mi_aov_cfg)]; lib.mi_aov_channel_count.restype = C.c_int32
+    lib.mi_render_sensor.argtypes = [vp, C.POINTER(mi_render_cfg), C.POINTER(mi_sensor_desc), vp]; lib.mi_render_sensor.restype = C.c_int32
+    lib.mi_sensor_sample_ray.argtypes = [vp, C.POINTER(mi_render_cfg), C.POINTER(mi_sensor_desc), vp, vp, vp, C.POINTER(mi_rays_soa), vp, vp,
+                                         C.c_uint64, C.c_int32]
+    lib.mi_sensor_sample_ray.restype = C.c_int32
     return lib
 
 
@@ -294,6 +304,8 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_integrator_sample_cfg": (i32, [vp, C.POINTER(mi_sample_cfg)]),
         "mih_sensor_create": (vp, [vp, vp, vp]), "mih_sensor_destroy": (None, [vp]),
         "mih_sensor_sample_ray": (i32, [vp, f, f, c_float_p]), "mih_sensor_x_fov": (f, [vp]),
+        "mih_sensor_sample_rays": (i32, [vp, c_float_p, c_float_p, c_float_p, u64]), "mih_sensor_desc": (i32, [vp, C.POINTER(mi_sensor_desc)]),
+        "mih_sensor_needs_aperture_sample": (i32, [vp]),
         "mih_integrator_create": (vp, [vp]), "mih_integrator_destroy": (None, [vp]),
         "mih_integrator_create_aov": (vp, [vp, C.POINTER(vp), C.POINTER(cp), u32]), "mih_integrator_aov_cfg": (i32, [vp, C.POINTER(mi_aov_cfg)]),
         "mih_film_set_channels": (i32, [vp, cp, c_float_p, u64]), "mih_film_bitmap_channels": (i32, [vp, C.c_char_p, u32, c_float_p, u64]),

@@ -26,7 +26,7 @@
 
 #include "../../include/miwave.h"
 #include "kernel_pick.h"
-#if defined(MIW_CLASS_PART) || defined(MIW_AOV_UNIT)   /* miwave_class.hip, miwave_aov.hip: the kernel headers alone */
+#if defined(MIW_CLASS_PART) || defined(MIW_AOV_UNIT) || defined(MIW_SENSOR_UNIT)   /* miwave_class.hip, miwave_aov.hip, miwave_sensor.hip: the kernel headers alone */
 #define MIW_KERNELS_ONLY 1
 #endif
 // Section clock (debug builds, -DMIW_SECTION_PROFILE=1): wall cycles per wavefront between markers, summed
@@ -118,6 +118,14 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/aov_launch.h"         /* the aov integrator's kernels (mi_render_aov): compiled in miwave_aov.hip (-DMIW_SPLIT_AOV=1), else here */
 #if defined(MIW_AOV_UNIT) || !defined(MIW_SPLIT_AOV)
 #include "device/aov_kernel.h"
+#endif
+#endif
+#if defined(MIW_SENSOR_UNIT) || !defined(MIW_KERNELS_ONLY)
+#include "miw/lens.h"
+#include "miw/film_gather_n.h"
+#include "device/sensor_launch.h"      /* the general sensor route's kernels (mi_render_sensor): compiled in miwave_sensor.hip (-DMIW_SPLIT_SENSOR=1), else here */
+#if defined(MIW_SENSOR_UNIT) || !defined(MIW_SPLIT_SENSOR)
+#include "device/sensor_kernel.h"
 #endif
 #endif
 
@@ -2782,6 +2790,7 @@ mi_status mi_selftest(mi_ctx *c, int32_t which, uint64_t *mismatches) {
 }
 
 #include "aov_host.h"                  /* mi_render_aov, mi_aov_channel_count */
+#include "sensor_host.h"               /* mi_render_sensor, mi_sensor_sample_ray */
 
 } // extern "C"
 #endif // !MIW_KERNELS_ONLY

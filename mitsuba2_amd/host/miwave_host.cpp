@@ -18,6 +18,7 @@
 #include "../csrc/miw/special.h"
 #include "../csrc/miw/aov.h"
 #include "../csrc/miw/film_gather_n.h"
+#include "../csrc/miw/lens.h"
 #include <cctype>
 
 namespace miwave {

@@ -268,6 +268,23 @@ public:
     std::array<float, 2> principal_point_offset() const { return m_pp_offset; }
     // perspective.cpp:182-216 (position_sample already divided by the crop size)
     Ray3f sample_ray(const std::array<float, 2> &position_sample) const;
+    // Sensor::sample_ray of this sensor's kind through the shared leaf (csrc/miw/lens.h: sensor_sample); the perspective kind
+    // ignores the aperture sample and returns sample_ray(position_sample) bit for bit
+    Ray3f sample_ray(const std::array<float, 2> &position_sample, const std::array<float, 2> &aperture_sample) const;
+    // what the general sensor route (mi_render_sensor, mi_sensor_sample_ray) takes beside the camera fields of mi_render_cfg
+    mi_sensor_desc desc() const;
+    bool is_thinlens() const { return m_kind == MI_SENSOR_THINLENS; }
+    bool needs_aperture_sample() const { return m_kind == MI_SENSOR_THINLENS; }   // sensor.h: m_needs_sample_3 (thinlens.cpp:145)
+    float shutter_open() const { return m_shutter_open; }
+    float shutter_open_time() const { return m_shutter_open_time; }
+    float aperture_radius() const { return m_aperture_radius; }
+    float focus_distance() const { return m_focus_distance; }
+protected:
+    // the projective state both cameras share (sensor.cpp:94-107, perspective_projection); kind = MI_SENSOR_*
+    PerspectiveCamera(const Properties &props, std::shared_ptr<Film> film, std::shared_ptr<IndependentSampler> sampler, int kind);
+    int m_kind = MI_SENSOR_PERSPECTIVE;
+    float m_aperture_radius = 0.f, m_focus_distance = 0.f;
+    float m_shutter_open = 0.f, m_shutter_open_time = 0.f;     // read by ThinLensCamera alone
 private:
     void update_camera_transforms();                           // :118-141
     std::shared_ptr<Film> m_film;
@@ -276,6 +293,15 @@ private:
     float m_near_clip, m_far_clip, m_x_fov;
     std::array<float, 2> m_pp_offset;
 };
+// src/sensors/thinlens.cpp: the projective state of PerspectiveCamera (no principal point offset) plus aperture_radius (required;
+// 0 becomes Epsilon with a warning), focus_distance (default far_clip, sensor.cpp:98) and the shutter (sensor.cpp:16-20). A handle
+// of a PerspectiveCamera may hold one: SamplingIntegrator::render looks at is_thinlens().
+class ThinLensCamera : public PerspectiveCamera {
+public:
+    explicit ThinLensCamera(const Properties &props, std::shared_ptr<Film> film, std::shared_ptr<IndependentSampler> sampler);
+};
+// `perspective` or `thinlens`; any other plugin name: Plugin "..." not found!
+std::shared_ptr<PerspectiveCamera> make_sensor(const Properties &props, std::shared_ptr<Film> film, std::shared_ptr<IndependentSampler> sampler);
 float parse_fov(const Properties &props, float aspect);       // src/librender/sensor.cpp:113-167
 
 // ---- BSDF plugins ----------------------------------------------------------------------------
@@ -617,6 +643,8 @@ public:
     void fill_sample_cfg(mi_sample_cfg &cfg) const;            // from fill_integrator
     // all passes of one job into `film5` (crop_w * crop_h * 5 floats); moment_pass = mi_render_cfg::moment_pass
     bool render_passes(Scene *scene, PerspectiveCamera *sensor, float *film5, int moment_pass);
+    // a sensor the resident kernels do not know (ThinLensCamera): the same passes through mi_render_sensor; one device, no shards
+    bool render_sensor_passes(Scene *scene, PerspectiveCamera *sensor, float *film5);
 protected:
     // one pass of a frame over the contexts of a multi-GPU scene: every context its shard on its own host thread, then the film reduce
     bool render_pass_multi(Scene *scene, PerspectiveCamera *sensor, float *film5, int moment_pass, uint32_t pass);
@@ -703,7 +731,7 @@ std::shared_ptr<SamplingIntegrator> make_integrator(const Properties &props);
 // ---- XML scene front-end, a subset (src/libcore/xml.cpp) --------------------------
 // <scene>, <default>, <include>, <alias>, $parameters (also from `params`), <shape type="obj|ply|rectangle|sphere">, <bsdf> (inline, or
 // top-level with id + <ref id=.../>), <texture type="bitmap"> (PFM files; nested in a <bsdf> under the parameter's
-// name, or top-level with id + <ref id=... name=.../>), <emitter type="area">, <emitter type="envmap"> (PFM file), <sensor type="perspective"> with <film>,
+// name, or top-level with id + <ref id=... name=.../>), <emitter type="area">, <emitter type="envmap"> (PFM file), <sensor type="perspective"> or <sensor type="thinlens"> with <film>,
 // <sampler>, <rfilter> children, <integrator type="path|direct">, <integrator type="moment|aov"> around a nested <integrator>; values <float> <integer> <boolean> <string> <rgb>
 // <spectrum value=...>; <transform name="to_world"> of <translate> <scale> <rotate> <lookat> <matrix>.
 // Anything else throws the reference's kind of error ("unexpected ..."/"Plugin ... not found").

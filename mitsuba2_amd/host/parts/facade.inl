@@ -414,8 +414,7 @@ void mih_sampler_set_state(void *s, uint64_t state, uint64_t inc) { ((Box<Indepe
 void *mih_sensor_create(void *props, void *film, void *sampler) {
     MIH_TRY
         const Properties &p = *(Properties *) props;
-        if (p.plugin_name() != "perspective") throw std::runtime_error("Plugin \"" + p.plugin_name() + "\" not found!");
-        return new Box<PerspectiveCamera>{ std::make_shared<PerspectiveCamera>(
+        return new Box<PerspectiveCamera>{ make_sensor(                      // "perspective" | "thinlens"
             p, film ? ((Box<Film> *) film)->p : nullptr, sampler ? ((Box<IndependentSampler> *) sampler)->p : nullptr) }; MIH_CATCH(nullptr)
 }
 void mih_sensor_destroy(void *s) { delete (Box<PerspectiveCamera> *) s; }
@@ -426,6 +425,20 @@ int mih_sensor_sample_ray(void *s, float x, float y, float *out8) {
         out8[6] = r.mint; out8[7] = r.maxt; return 0; MIH_CATCH(-1)
 }
 float mih_sensor_x_fov(void *s) { return ((Box<PerspectiveCamera> *) s)->p->x_fov(); }
+// Sensor::sample_ray(position, aperture) for n samples through the shared leaf (csrc/miw/lens.h); aperture NULL = (.5, .5). out: n x 8
+int mih_sensor_sample_rays(void *s, const float *position, const float *aperture, float *out8, uint64_t n) {
+    MIH_TRY
+        const PerspectiveCamera *cam = ((Box<PerspectiveCamera> *) s)->p.get();
+        for (uint64_t i = 0; i < n; ++i) {
+            Ray3f r = cam->sample_ray({ position[2 * i], position[2 * i + 1] },
+                                      aperture ? std::array<float, 2>{ aperture[2 * i], aperture[2 * i + 1] } : std::array<float, 2>{ .5f, .5f });
+            float *o = out8 + 8 * i;
+            o[0] = r.o[0]; o[1] = r.o[1]; o[2] = r.o[2]; o[3] = r.d[0]; o[4] = r.d[1]; o[5] = r.d[2]; o[6] = r.mint; o[7] = r.maxt;
+        }
+        return 0; MIH_CATCH(-1)
+}
+int mih_sensor_desc(void *s, mi_sensor_desc *out) { MIH_TRY *out = ((Box<PerspectiveCamera> *) s)->p->desc(); return 0; MIH_CATCH(-1) }
+int mih_sensor_needs_aperture_sample(void *s) { return ((Box<PerspectiveCamera> *) s)->p->needs_aperture_sample() ? 1 : 0; }
 
 void *mih_integrator_create(void *props) {
     MIH_TRY

@@ -276,7 +276,10 @@ float parse_fov(const Properties &props, float aspect) {
 
 PerspectiveCamera::PerspectiveCamera(const Properties &props, std::shared_ptr<Film> film,
                                      std::shared_ptr<IndependentSampler> sampler)
-    : m_film(std::move(film)), m_sampler(std::move(sampler)) {
+    : PerspectiveCamera(props, std::move(film), std::move(sampler), MI_SENSOR_PERSPECTIVE) { }
+PerspectiveCamera::PerspectiveCamera(const Properties &props, std::shared_ptr<Film> film,
+                                     std::shared_ptr<IndependentSampler> sampler, int kind)
+    : m_kind(kind), m_film(std::move(film)), m_sampler(std::move(sampler)) {
     if (!m_film) m_film = std::make_shared<Film>();
     if (!m_sampler) m_sampler = std::make_shared<IndependentSampler>();
     m_near_clip = props.float_("near_clip", 1e-2f);            // sensor.cpp:94-96
@@ -289,8 +292,48 @@ PerspectiveCamera::PerspectiveCamera(const Properties &props, std::shared_ptr<Fi
     if (m_to_world.has_scale()) Throw("Scale factors in the camera-to-world transformation are not allowed!");
     update_camera_transforms();
     auto crop = m_film->crop_size();
-    m_pp_offset = { props.float_("principal_point_offset_x", 0.f) * ((float) size[0] / (float) crop[0]),
-                    props.float_("principal_point_offset_y", 0.f) * ((float) size[1] / (float) crop[1]) };
+    m_pp_offset = { 0.f, 0.f };                                // (the thin lens has no principal point offset)
+    if (m_kind == MI_SENSOR_PERSPECTIVE)
+        m_pp_offset = { props.float_("principal_point_offset_x", 0.f) * ((float) size[0] / (float) crop[0]),
+                        props.float_("principal_point_offset_y", 0.f) * ((float) size[1] / (float) crop[1]) };
+}
+// thinlens.cpp:110-146 over ProjectiveCamera (sensor.cpp:94-107) and Sensor (sensor.cpp:16-20)
+ThinLensCamera::ThinLensCamera(const Properties &props, std::shared_ptr<Film> film, std::shared_ptr<IndependentSampler> sampler)
+    : PerspectiveCamera(props, std::move(film), std::move(sampler), MI_SENSOR_THINLENS) {
+    m_shutter_open = props.float_("shutter_open", 0.f);        // sensor.cpp:16-20
+    m_shutter_open_time = props.float_("shutter_close", 0.f) - m_shutter_open;
+    if (m_shutter_open_time < 0.f) Throw("Shutter opening time must be less than or equal to the shutter closing time!");
+    m_focus_distance = props.float_("focus_distance", far_clip());   // sensor.cpp:98
+    m_aperture_radius = props.float_("aperture_radius");       // :114
+    if (m_aperture_radius == 0.f) {                            // :116-119
+        std::fprintf(stderr, "[miwave_host] warning: Can't have a zero aperture radius -- setting to %g\n", (double) MIW_EPSILON);
+        m_aperture_radius = MIW_EPSILON;
+    }
+}
+std::shared_ptr<PerspectiveCamera> make_sensor(const Properties &props, std::shared_ptr<Film> film, std::shared_ptr<IndependentSampler> sampler) {
+    if (props.plugin_name() == "perspective") return std::make_shared<PerspectiveCamera>(props, std::move(film), std::move(sampler));
+    if (props.plugin_name() == "thinlens") return std::make_shared<ThinLensCamera>(props, std::move(film), std::move(sampler));
+    Throw("Plugin \"" + props.plugin_name() + "\" not found!");
+}
+mi_sensor_desc PerspectiveCamera::desc() const {
+    mi_sensor_desc d;
+    std::memset(&d, 0, sizeof d);
+    d.struct_size = (uint32_t) sizeof d; d.type = m_kind;
+    d.aperture_radius = m_aperture_radius; d.focus_distance = m_focus_distance;
+    d.shutter_open = m_shutter_open; d.shutter_open_time = m_shutter_open_time;
+    return d;
+}
+Ray3f PerspectiveCamera::sample_ray(const std::array<float, 2> &position_sample, const std::array<float, 2> &aperture_sample) const {
+    miw::SensorRec s;
+    std::memcpy(s.sample_to_camera, m_sample_to_camera.m, 64);
+    std::memcpy(s.to_world, m_to_world.m, 64);
+    s.near_clip = m_near_clip; s.far_clip = m_far_clip; s.pp_offset[0] = m_pp_offset[0]; s.pp_offset[1] = m_pp_offset[1];
+    miw::LensRec l;
+    l.kind = m_kind == MI_SENSOR_THINLENS ? (uint32_t) miw::LENS_THINLENS : (uint32_t) miw::LENS_PERSPECTIVE;
+    l.aperture_radius = m_aperture_radius; l.focus_distance = m_focus_distance; l.draw_time = m_shutter_open_time > 0.f ? 1u : 0u;
+    miw::Ray r = miw::sensor_sample(s, l, miw::v2(position_sample[0], position_sample[1]), miw::v2(aperture_sample[0], aperture_sample[1]));
+    Ray3f out; out.o = { r.o.x, r.o.y, r.o.z }; out.d = { r.d.x, r.d.y, r.d.z }; out.mint = r.mint; out.maxt = r.maxt;
+    return out;
 }
 void PerspectiveCamera::update_camera_transforms() {
     // perspective_projection, include/mitsuba/render/sensor.h:196-231

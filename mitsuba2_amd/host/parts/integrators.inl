@@ -218,11 +218,35 @@ bool SamplingIntegrator::render_passes(Scene *scene, PerspectiveCamera *sensor, 
     }
     return true;
 }
+// The thinlens sensor changes render_sample's draw ledger (integrator.cpp:244-250), which the resident kernels have compiled in:
+// its frames go through the general sensor route, which serves sample() of path and direct on one context.
+static const char *const THINLENS_SERVED = "The thinlens sensor is served for the path and direct integrators only, on one device and without tile shards (mi_render_sensor).";
+bool SamplingIntegrator::render_sensor_passes(Scene *scene, PerspectiveCamera *sensor, float *film5) {
+    if (scene->device_count() > 1 || m_world > 1) Throw(THINLENS_SERVED);
+    const mi_sensor_desc desc = sensor->desc();
+    const uint32_t passes = pass_count(sensor);
+    mi_counters total{};
+    m_last_reduce = MI_REDUCE_NONE;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        mi_render_cfg cfg; std::vector<uint32_t> block_ids, tiles;
+        make_render_cfg(sensor, cfg, block_ids, tiles, 1, pass);
+        m_active_ctx.store(scene->ctx());
+        mi_status st = mi_render_sensor(scene->ctx(), &cfg, &desc, film5);
+        m_active_ctx.store(nullptr);
+        mi_get_counters(scene->ctx(), &m_counters);
+        if (pass > 0) { m_counters.samples += total.samples; m_counters.ms_render += total.ms_render; }
+        total = m_counters;
+        if (st == MI_ERR_CANCELLED) return false;
+        if (st != MI_OK) Throw(std::string("mi_render_sensor: ") + mi_last_error(scene->ctx()));
+    }
+    return true;
+}
 bool SamplingIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
     if (!scene || !sensor) Throw("render(): null scene or sensor");
     if (!scene->ctx()) Throw("render(): the scene has no device context (Scene::build(device >= 0) first)");
     Film *film = sensor->film().get();
     film->prepare({ "X", "Y", "Z", "A", "W" });                // integrator.cpp:67-73
+    if (sensor->is_thinlens()) return render_sensor_passes(scene, sensor, film->storage().data());
     return render_passes(scene, sensor, film->storage().data(), MI_MOMENT_OFF);
 }
 
@@ -270,6 +294,7 @@ std::vector<std::string> MomentIntegrator::aov_names() const {
 }
 bool MomentIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
     if (!scene || !sensor) Throw("render(): null scene or sensor");
+    if (sensor->is_thinlens()) Throw(THINLENS_SERVED);
     if (!scene->ctx()) Throw("render(): the scene has no device context (Scene::build(device >= 0) first)");
     Film *film = sensor->film().get();
     std::vector<std::string> channels = { "X", "Y", "Z", "A", "W" };
@@ -360,6 +385,7 @@ void AOVIntegrator::fill_aov_cfg(mi_aov_cfg &a) const {
 }
 bool AOVIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
     if (!scene || !sensor) Throw("render(): null scene or sensor");
+    if (sensor->is_thinlens()) Throw(THINLENS_SERVED);
     if (!scene->ctx()) Throw("render(): the scene has no device context (Scene::build(device >= 0) first)");
     if (scene->device_count() > 1 || m_world > 1) Throw("aov: a frame with AOV channels is rendered by one context (no multi-GPU scenes, no tile shards)");
     Film *film = sensor->film().get();

@@ -286,7 +286,7 @@ LoadedScene load_xml_string(const std::string &xml, const std::map<std::string, 
             }
         } else if (n.tag == "sensor") {
             Properties p(cx.get(n, "type"));
-            if (p.plugin_name() != "perspective") Throw("Plugin \"" + p.plugin_name() + "\" not found!");
+            if (p.plugin_name() != "perspective" && p.plugin_name() != "thinlens") Throw("Plugin \"" + p.plugin_name() + "\" not found!");
             std::shared_ptr<Film> film; std::shared_ptr<IndependentSampler> sampler;
             for (const XmlNode *c : parse_properties(cx, n, p)) {
                 if (c->tag == "film") {
@@ -308,7 +308,7 @@ LoadedScene load_xml_string(const std::string &xml, const std::map<std::string, 
             }
             if (!film) film = std::make_shared<Film>(Properties("hdrfilm"));               // sensor.cpp:60-66 defaults
             if (!sampler) sampler = std::make_shared<IndependentSampler>(Properties("independent"));
-            out.sensor = std::make_shared<PerspectiveCamera>(p, film, sampler);
+            out.sensor = make_sensor(p, film, sampler);
         } else if (n.tag == "emitter") {
             Properties p(cx.get(n, "type"));
             const std::string &en = p.plugin_name();

@@ -137,12 +137,20 @@ def cornell_box_meshes(diffuse_only=True, ball_level=5, metal=None, glass=None, 
     return meshes
 
 
-def cornell_sensor(width, height, spp, seed=0, rfilter="gaussian", **film_kw):
+def cornell_sensor(width, height, spp, seed=0, rfilter="gaussian", sensor=None, **film_kw):
+    """The Cornell camera. `sensor` (every builder below hands its keywords on to here): None = the perspective camera; a
+    dict(type="thinlens", aperture_radius=..., ...) = that plugin at the same place, its other entries the plugin's properties; or
+    a callable (film, sampler) -> sensor."""
     film = api.Film(rfilter=rfilter, width=width, height=height, **film_kw)
     sampler = api.Sampler(sample_count=spp, seed=seed)
-    sensor = api.Sensor(film, sampler, fov=39.3,
-                        to_world=dict(origin=(278, 273, -800), target=(278, 273, 0), up=(0, 1, 0)))
-    return sensor
+    if callable(sensor):
+        return sensor(film, sampler)
+    kw = dict(fov=39.3, to_world=dict(origin=(278, 273, -800), target=(278, 273, 0), up=(0, 1, 0)))
+    kw.update(sensor or {})
+    kind = kw.pop("type", "perspective")
+    if kind not in ("perspective", "thinlens"):
+        raise ValueError("cornell_sensor: unknown sensor type %r" % (kind,))
+    return (api.ThinLensCamera if kind == "thinlens" else api.Sensor)(film, sampler, **kw)
 
 
 def cornell_box(width, height, spp, diffuse_only=True, seed=0, device=0, ball_level=5, rfilter="gaussian",
