@@ -186,6 +186,19 @@ typedef struct {
                                               the set_scene enlargement (max(RayEpsilon, r (1 + RayEpsilon))) itself        */
 } mi_light;
 
+/* HomogeneousMedium (src/media/homogeneous.cpp, src/librender/medium.cpp) after its constructor ran, with its phase function
+ * (src/phase/isotropic.cpp, hg.cpp). scalar_rgb library. mi_scene_upload refuses, naming the record: a sigma_t channel that is
+ * not finite and > 0 (volpath.cpp:123 would divide 0 / 0), an albedo channel outside [0, 1], |g| >= 1, an unknown phase type. */
+enum { MI_PHASE_ISOTROPIC = 0, MI_PHASE_HG = 1 };
+typedef struct mi_medium {
+    float sigma_t[3];                      /* `sigma_t` times `scale` (homogeneous.cpp:30-32)                              */
+    float albedo[3];                       /* `albedo` (default 0.75)                                                      */
+    uint32_t has_spectral_extinction;      /* homogeneous.cpp:27, default 1                                                */
+    uint32_t sample_emitters;              /* medium.cpp:29, default 1                                                     */
+    uint32_t phase;                        /* MI_PHASE_*                                                                   */
+    float g;                               /* hg: the asymmetry parameter, in (-1, 1)                                      */
+} mi_medium;                               /* 10 words */
+
 typedef struct {
     const float    *vertex_positions;  /* 3 * vertex_count                               */
     const float    *vertex_normals;    /* 3 * vertex_count, or NULL                      */
@@ -210,6 +223,14 @@ typedef struct {
     /* point / spot / directional / constant emitters, or NULL / 0 (appended: the members above keep their offsets). At most one
      * environment emitter per scene: a MI_LIGHT_CONSTANT record excludes `envmap` and a second constant record. */
     const mi_light *lights; uint32_t light_count;
+    /* participating media (appended: the members above keep their offsets; a zero-initialised description has none). Read by
+     * MI_INTEGRATOR_VOLPATH only: path, direct and aov ignore them, as the reference's do. Every medium REFERENCE is index + 1,
+     * 0 = no medium.
+     *   shape_media   NULL, or two references per shape: interior, then exterior (Shape::interior_medium / exterior_medium)
+     *   start_medium  the medium the sensor — or the caller's rays (mi_sample) — start in (Sensor::medium)                    */
+    const struct mi_medium *media; uint32_t media_count;
+    const uint32_t *shape_media;
+    uint32_t start_medium;
 } mi_scene_desc;
 enum { MI_ROUGH_TRANSMITTANCE_RES = 64 };
 
@@ -300,7 +321,11 @@ enum { MI_MOMENT_OFF = 0, MI_MOMENT_VALUES = 1, MI_MOMENT_SQUARES = 2 };
 enum { MI_FILM_REPLAY_AUTO = 0, MI_FILM_REPLAY_BLOCKS = 1 /* 24-byte position log + k_film_blocks */, MI_FILM_REPLAY_GROUPS = 2, MI_FILM_REPLAY_COLUMNS = 3,
        MI_FILM_REPLAY_QUADS = 4, MI_FILM_REPLAY_LANES = 5 /* tile-interleaved log */, MI_FILM_REPLAY_LANES_PLAIN_LOG = 6 };
 enum { MI_PATH_KERNEL_AUTO = 0, MI_PATH_KERNEL_LOCKSTEP = 1, MI_PATH_KERNEL_PHASED = 2, MI_PATH_KERNEL_POOLED = 3 };
-enum { MI_INTEGRATOR_PATH = 0, MI_INTEGRATOR_DIRECT = 1 };
+enum { MI_INTEGRATOR_PATH = 0, MI_INTEGRATOR_DIRECT = 1,
+       /* VolumetricPathIntegrator (src/integrators/volpath.cpp:60-465) over the media records of mi_scene_desc: max_depth, rr_depth and
+        * hide_emitters apply. Served by mi_sample and mi_render_sensor (scalar_rgb library); mi_render, mi_render_aov and the
+        * moment integrator refuse it by name. */
+       MI_INTEGRATOR_VOLPATH = 2 };
 
 typedef struct {
     uint64_t samples;          /* camera samples finished                               */
@@ -452,13 +477,14 @@ mi_status mi_pdf_emitter_direction(mi_ctx *ctx, int32_t emitter, const float *re
 mi_status mi_emitter_eval(mi_ctx *ctx, const mi_surface_interaction *si, const float *wavelengths, float *spec, uint64_t n);
 
 /* SamplingIntegrator::sample(scene, sampler, ray) -> (Spectrum, Mask) (include/mitsuba/render/integrator.h:114-119) for n
- * caller-supplied rays: PathIntegrator::sample (path.cpp:100-211) or DirectIntegrator::sample (direct.cpp:105-198). The moment
- * integrator is NOT served (its sample() returns AOVs); neither are ray differentials and media. */
+ * caller-supplied rays: PathIntegrator::sample (path.cpp:100-211), DirectIntegrator::sample (direct.cpp:105-198) or
+ * VolumetricPathIntegrator::sample (volpath.cpp:60-257; the rays start in mi_scene_desc::start_medium). The moment
+ * integrator is NOT served (its sample() returns AOVs); neither are ray differentials. */
 typedef struct {
     uint32_t struct_size;            /* sizeof(mi_sample_cfg) of the caller: the library refuses a size it does not know */
-    int32_t  integrator;             /* MI_INTEGRATOR_PATH | MI_INTEGRATOR_DIRECT                                        */
-    int32_t  max_depth, rr_depth;    /* path                                                                             */
-    uint32_t emitter_samples, bsdf_samples;  int32_t hide_emitters;   /* direct                                         */
+    int32_t  integrator;             /* MI_INTEGRATOR_PATH | MI_INTEGRATOR_DIRECT | MI_INTEGRATOR_VOLPATH                */
+    int32_t  max_depth, rr_depth;    /* path, volpath                                                                    */
+    uint32_t emitter_samples, bsdf_samples;  int32_t hide_emitters;   /* direct; hide_emitters: volpath too             */
     int32_t  on_device;              /* 0: every pointer below is a host pointer; 1: device pointers (no copies)          */
 } mi_sample_cfg;                     /* 8 words */
 /*   rays        SoA, as for mi_trace (o, d, mint, maxt)
@@ -563,6 +589,10 @@ mi_status mi_film_download(mi_ctx *ctx, const void *device_film, float *host, ui
 mi_status mi_film_reduce(mi_ctx *const *ctxs, void *const *films, int32_t n, uint64_t count, int32_t root, int32_t *how);
 
 mi_status   mi_get_counters(mi_ctx *ctx, mi_counters *out);
+/* MI_INTEGRATOR_VOLPATH: the rays of the last mi_sample / mi_render_sensor call whose lane loop ran past MIW_VOLPATH_MAX_TRIPS (65536)
+ * trips and were ended with L = 0, valid = 0 — 0 for every real path (the bound is there so that every loop ends on a shared GPU).
+ * An entry point of its own: mi_counters keeps the layout and the last members its callers know. */
+mi_status   mi_volpath_capped(mi_ctx *ctx, uint64_t *out);
 const char *mi_last_error(mi_ctx *ctx);
 
 /* Device-side evaluation of the leaf functions, for known-answer parity tests
@@ -583,8 +613,14 @@ enum {
     MI_EVAL_INVTRIG = 10,         /* in: y, x                            out: atan2(y,x), acos(x), asin(x) (3)       */
     MI_EVAL_SPECTRUM = 11,        /* spectral library only. in: wavelength sample, c0,c1,c2, d65 scale (5)
                                      out: wavelengths[4], weights[4], srgb[4], srgb_d65[4], xyz of weight*srgb_d65 (19) */
-    MI_EVAL_TEXTURE = 12          /* BitmapTexture::eval at si.uv. in: u, v, (float) bitmap index, wavelength sample (4)
+    MI_EVAL_TEXTURE = 12,         /* BitmapTexture::eval at si.uv. in: u, v, (float) bitmap index, wavelength sample (4)
                                      out: the texture's Spectrum (3 / 4)                                             */
+    /* the leaves of the uploaded media (scalar_rgb library; `medium` = (float) index into mi_scene_desc::media):
+     * Medium::sample_interaction(ray, sample, channel), then eval_tr_and_pdf against a surface at si_t (volpath.cpp:105-114) */
+    MI_EVAL_MEDIUM = 13,          /* in: medium, o.xyz, d.xyz, mint, maxt, sample, channel, si_t (12)
+                                     out: t, mint, p.xyz, sigma_s[3], sigma_t[3], combined_extinction[3], sampled_t, 0, tr[3], pdf[3] (22) */
+    MI_EVAL_PHASE = 14            /* PhaseFunction::sample / eval of that medium's phase function for a ray of direction ray_d (= -wi).
+                                     in: medium, ray_d.xyz, sample2, wo.xyz (9)   out: sampled wo.xyz, pdf, eval(wo) (5) */
 };
 mi_status mi_eval(mi_ctx *ctx, int32_t op, const mi_render_cfg *cfg,
                   const float *in, int32_t in_stride, float *out, int32_t out_stride, uint64_t n);

@@ -62,6 +62,11 @@ class mi_bitmap(C.Structure):
                 ("filter_type", C.c_uint32), ("wrap_mode", C.c_uint32), ("to_uv", C.c_float * 6)]
 
 
+class mi_medium(C.Structure):
+    _fields_ = [("sigma_t", C.c_float * 3), ("albedo", C.c_float * 3), ("has_spectral_extinction", C.c_uint32),
+                ("sample_emitters", C.c_uint32), ("phase", C.c_uint32), ("g", C.c_float)]
+
+
 class mi_scene_desc(C.Structure):
     _fields_ = [("vertex_positions", c_float_p), ("vertex_normals", c_float_p), ("vertex_count", C.c_uint32),
                 ("faces", c_u32_p), ("face_count", C.c_uint32),
@@ -73,7 +78,8 @@ class mi_scene_desc(C.Structure):
                 ("spheres", C.POINTER(mi_sphere)), ("sphere_count", C.c_uint32),
                 ("vertex_texcoords", c_float_p), ("bitmaps", C.POINTER(mi_bitmap)), ("bitmap_count", C.c_uint32),
                 ("bsdf_tables", c_float_p), ("bsdf_table_floats", C.c_uint32),
-                ("lights", C.POINTER(mi_light)), ("light_count", C.c_uint32)]
+                ("lights", C.POINTER(mi_light)), ("light_count", C.c_uint32),
+                ("media", C.POINTER(mi_medium)), ("media_count", C.c_uint32), ("shape_media", c_u32_p), ("start_medium", C.c_uint32)]
 
 
 class mi_rays_soa(C.Structure):
@@ -154,7 +160,8 @@ class mi_sensor_desc(C.Structure):
                 ("shutter_open", C.c_float), ("shutter_open_time", C.c_float), ("debug_group_tiles", C.c_uint32)]
 
 
-MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT = 0, 1
+MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT, MI_INTEGRATOR_VOLPATH = 0, 1, 2
+MI_PHASE_ISOTROPIC, MI_PHASE_HG = 0, 1
 MI_SENSOR_PERSPECTIVE, MI_SENSOR_THINLENS = 0, 1
 # mi_aov_cfg::types in the order of aov.cpp's grammar, and mi_aov_cfg::nested
 MI_AOV = dict(depth=0, position=1, uv=2, geo_normal=3, sh_normal=4, dp_du=5, dp_dv=6, duv_dx=7, duv_dy=8)
@@ -169,7 +176,7 @@ MI_LIGHT_POINT, MI_LIGHT_SPOT, MI_LIGHT_DIRECTIONAL, MI_LIGHT_CONSTANT = range(4
 MI_BVH_FORCE_TREE, MI_BVH_NO_LEAF_FILTER, MI_BVH_RADIX_TREE = 0x10, 0x20, 0x40      # flags of mi_bvh_build's quality argument
 MI_OK, MI_ERR_INVALID, MI_ERR_DEVICE, MI_ERR_STATE, MI_ERR_CANCELLED = 0, -1, -2, -3, -4
 MI_EVAL = dict(PCG32=0, SINCOS=1, COSINE_HEMISPHERE=2, BSDF=3, FRESNEL=4, CAMERA_RAY=5, EMITTER_SAMPLE=6,
-               FP_SEMANTICS=7, SPECIAL=8, ENVMAP=9, INVTRIG=10, SPECTRUM=11, TEXTURE=12)
+               FP_SEMANTICS=7, SPECIAL=8, ENVMAP=9, INVTRIG=10, SPECTRUM=11, TEXTURE=12, MEDIUM=13, PHASE=14)
 MI_EVAL_STRIDES = {0: (2, 8), 1: (1, 2), 2: (2, 4), 3: (10, 13), 4: (2, 4), 5: (2, 8), 6: (5, 14), 7: (3, 8), 8: (1, 4), 9: (8, 12), 10: (2, 3)}
 
 # every symbol include/miwave.h declares (tests check that the library exports all of them)
@@ -178,7 +185,7 @@ MI_SYMBOLS = ["mi_spectrum_channels", "mi_device_count", "mi_create", "mi_destro
               "mi_ray_intersect", "mi_sample_emitter_direction", "mi_pdf_emitter_direction", "mi_emitter_eval", "mi_sample",
               "mi_film_alloc", "mi_film_free", "mi_film_download", "mi_film_reduce",
               "mi_set_option", "mi_get_option", "mi_option_count", "mi_option_name", "mi_option_help",
-              "mi_render_aov", "mi_aov_channel_count", "mi_render_sensor", "mi_sensor_sample_ray"]
+              "mi_render_aov", "mi_aov_channel_count", "mi_render_sensor", "mi_sensor_sample_ray", "mi_volpath_capped"]
 
 
 VARIANT_SUFFIX = {"scalar_rgb": "", "scalar_spectral": "_spectral"}
@@ -197,6 +204,10 @@ def eval_strides(op, channels=3):
         return 5, 19
     if op == 12:
         return 4, channels
+    if op == 13:                                                 # MI_EVAL_MEDIUM
+        return 12, 22
+    if op == 14:                                                 # MI_EVAL_PHASE
+        return 9, 5
     return MI_EVAL_STRIDES[op]
 
 
@@ -243,6 +254,7 @@ def load_device_lib(variant="scalar_rgb"):
     lib.mi_sensor_sample_ray.argtypes = [vp, C.POINTER(mi_render_cfg), C.POINTER(mi_sensor_desc), vp, vp, vp, C.POINTER(mi_rays_soa), vp, vp,
                                          C.c_uint64, C.c_int32]
     lib.mi_sensor_sample_ray.restype = C.c_int32
+    lib.mi_volpath_capped.argtypes = [vp, C.POINTER(C.c_uint64)]; lib.mi_volpath_capped.restype = C.c_int32
     return lib
 
 
@@ -307,6 +319,12 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_sensor_sample_rays": (i32, [vp, c_float_p, c_float_p, c_float_p, u64]), "mih_sensor_desc": (i32, [vp, C.POINTER(mi_sensor_desc)]),
         "mih_sensor_needs_aperture_sample": (i32, [vp]),
         "mih_integrator_create": (vp, [vp]), "mih_integrator_destroy": (None, [vp]),
+        "mih_phase_create": (vp, [vp]), "mih_phase_destroy": (None, [vp]),
+        "mih_phase_sample_eval": (i32, [vp, c_float_p, c_float_p, c_float_p, c_float_p]),
+        "mih_medium_create": (vp, [vp, vp]), "mih_medium_destroy": (None, [vp]), "mih_medium_record": (i32, [vp, C.POINTER(mi_medium)]),
+        "mih_medium_sample_interaction": (i32, [vp, c_float_p, f, u32, f, c_float_p, c_float_p]),
+        "mih_mesh_set_media": (None, [vp, vp, vp]), "mih_mesh_is_medium_transition": (i32, [vp]),
+        "mih_scene_set_start_medium": (None, [vp, vp]), "mih_sensor_set_medium": (None, [vp, vp]),
         "mih_integrator_create_aov": (vp, [vp, C.POINTER(vp), C.POINTER(cp), u32]), "mih_integrator_aov_cfg": (i32, [vp, C.POINTER(mi_aov_cfg)]),
         "mih_film_set_channels": (i32, [vp, cp, c_float_p, u64]), "mih_film_bitmap_channels": (i32, [vp, C.c_char_p, u32, c_float_p, u64]),
         "mih_aov_fill": (i32, [i32, c_float_p, i32, c_float_p, c_float_p, i32, C.POINTER(C.c_uint8), u32, c_float_p, c_float_p]),
@@ -315,7 +333,7 @@ def load_host_lib(variant="scalar_rgb"):
         "mih_integrator_set_shard": (None, [vp, u32, u32]), "mih_integrator_set_profile": (None, [vp, i32]),
         "mih_integrator_set_plan": (None, [vp, i32]),
         "mih_integrator_cancel": (None, [vp]), "mih_integrator_render": (i32, [vp, vp, vp]),
-        "mih_integrator_counters": (i32, [vp, C.POINTER(mi_counters)]),
+        "mih_integrator_counters": (i32, [vp, C.POINTER(mi_counters)]), "mih_integrator_volpath_capped": (u64, [vp]),
         "mih_make_render_cfg": (i32, [vp, vp, C.POINTER(mi_render_cfg), c_u32_p, c_u32_p, u32, u32]),
         "mih_make_render_cfg_pass": (i32, [vp, vp, C.POINTER(mi_render_cfg), c_u32_p, c_u32_p, u32, u32, u32]),
         "mih_integrator_pass_count": (i32, [vp, vp]),

@@ -26,7 +26,7 @@
 
 #include "../../include/miwave.h"
 #include "kernel_pick.h"
-#if defined(MIW_CLASS_PART) || defined(MIW_AOV_UNIT) || defined(MIW_SENSOR_UNIT)   /* miwave_class.hip, miwave_aov.hip, miwave_sensor.hip: the kernel headers alone */
+#if defined(MIW_CLASS_PART) || defined(MIW_AOV_UNIT) || defined(MIW_SENSOR_UNIT) || defined(MIW_VOLPATH_UNIT)   /* miwave_class.hip, miwave_aov.hip, miwave_sensor.hip, miwave_volpath.hip: the kernel headers alone */
 #define MIW_KERNELS_ONLY 1
 #endif
 // Section clock (debug builds, -DMIW_SECTION_PROFILE=1): wall cycles per wavefront between markers, summed
@@ -126,6 +126,13 @@ static_assert(sizeof(TexRec) == sizeof(mi_texture), "texture record layout");
 #include "device/sensor_launch.h"      /* the general sensor route's kernels (mi_render_sensor): compiled in miwave_sensor.hip (-DMIW_SPLIT_SENSOR=1), else here */
 #if defined(MIW_SENSOR_UNIT) || !defined(MIW_SPLIT_SENSOR)
 #include "device/sensor_kernel.h"
+#endif
+#endif
+#if defined(MIW_VOLPATH_UNIT) || !defined(MIW_KERNELS_ONLY)
+#include "miw/volpath.h"
+#include "device/volpath_launch.h"     /* the volpath integrator's kernels (mi_sample, mi_render_sensor): compiled in miwave_volpath.hip (-DMIW_SPLIT_VOLPATH=1), else here */
+#if defined(MIW_VOLPATH_UNIT) || !defined(MIW_SPLIT_VOLPATH)
+#include "device/volpath_kernel.h"
 #endif
 #endif
 
@@ -290,6 +297,9 @@ struct mi_ctx {
     uint32_t replay_launches = 0;
 
     DevBuf<unsigned char> d_sample_stage; DevBuf<uint32_t> d_next_ray;   // mi_sample: the staged chunk of a host-pointer call, the ray queue's counter
+    // participating media (MI_INTEGRATOR_VOLPATH; miw/medium.h): the records, per shape its interior / exterior reference, the medium rays start in
+    std::vector<MediumRec> media; std::vector<uint32_t> shape_media; uint32_t start_medium = 0;
+    DevBuf<MediumRec> d_media; DevBuf<uint32_t> d_shape_media, d_volpath_capped; uint64_t volpath_capped = 0;   // (the last call's count: mi_volpath_capped)
 
     std::vector<hipEvent_t> ev_pool;
     mi_counters counters{};
@@ -342,6 +352,7 @@ void mi_destroy(mi_ctx *c) {
     (void) hipSetDevice(c->device);
     (void) hipDeviceSynchronize();
     c->d_nodes.release(); c->d_tris.release(); c->d_tri_vn.release(); c->d_tri_uv.release(); c->d_bitmap_data.release(); c->d_bitmaps.release(); c->d_bsdf_tables.release(); c->d_shapes.release(); c->d_rects.release(); c->d_bsdfs.release();
+    c->d_media.release(); c->d_shape_media.release(); c->d_volpath_capped.release();
     c->d_emitters.release(); c->d_lights.release(); c->d_leaf_boxes.release(); c->d_tri_bounds.release(); c->d_nodes4.release(); c->d_nodes8.release(); c->d_tris8.release(); c->d_tri_vn8.release(); c->d_env_data.release(); c->d_env_levels.release(); c->d_env.release(); c->d_emit_tri.release(); c->d_emit_vnorm.release(); c->d_emit_pmf.release(); c->d_emit_cdf.release();
     c->q_tp.release(); c->q_res.release(); c->q_ray_o.release(); c->q_ray_d.release(); c->q_hit.release();
     c->q_sh_d.release(); c->q_sh_c.release(); c->q_st.release(); c->q_pos.release(); c->q_pixel.release(); c->q_sh_vis.release();
@@ -373,6 +384,12 @@ const char *mi_option_name(int32_t i) { return i >= 0 && i < mi_option_count() ?
 const char *mi_option_help(int32_t i) { return i >= 0 && i < mi_option_count() ? g_knobs[i].what : nullptr; }
 
 mi_status mi_cancel(mi_ctx *c) { if (!c) return MI_ERR_INVALID; c->cancel.store(1); return MI_OK; }
+
+mi_status mi_volpath_capped(mi_ctx *c, uint64_t *out) {
+    if (!c || !out) return MI_ERR_INVALID;
+    *out = c->volpath_capped;
+    return MI_OK;
+}
 
 mi_status mi_get_counters(mi_ctx *c, mi_counters *out) {
     if (!c || !out) return MI_ERR_INVALID;
@@ -476,6 +493,36 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     if (!s->shapes || s->shape_count == 0) return fail(c, MI_ERR_INVALID, "scene: no shapes");
     if (!s->bsdfs || s->bsdf_count == 0) return fail(c, MI_ERR_INVALID, "scene: no bsdfs");
     if (s->face_count >= (1u << 27) - 16u) return fail(c, MI_ERR_INVALID, "scene: too many faces");   // leaf codes (first << 4 | count - 1) must stay clear of MIW_BVH4_ABSENT / MIW_WALK_DONE
+
+    // participating media (read by MI_INTEGRATOR_VOLPATH alone): HomogeneousMedium records, references = index + 1, 0 = none
+    if (s->media_count && !s->media) return fail(c, MI_ERR_INVALID, "scene: media_count without media");
+    if (s->start_medium > s->media_count) return fail(c, MI_ERR_INVALID, "scene: start_medium %u out of range (%u media; a reference is index + 1)", s->start_medium, s->media_count);
+    for (uint32_t k = 0; k < s->media_count; ++k) {
+        const mi_medium &m = s->media[k];
+        for (int a = 0; a < 3; ++a) {
+            if (!(std::isfinite(m.sigma_t[a]) && m.sigma_t[a] > 0.f)) return fail(c, MI_ERR_INVALID, "medium %u: sigma_t[%d] = %g must be finite and > 0", k, a, (double) m.sigma_t[a]);
+            if (!(m.albedo[a] >= 0.f && m.albedo[a] <= 1.f)) return fail(c, MI_ERR_INVALID, "medium %u: albedo[%d] = %g must lie in [0, 1]", k, a, (double) m.albedo[a]);
+        }
+        if (m.phase != MI_PHASE_ISOTROPIC && m.phase != MI_PHASE_HG) return fail(c, MI_ERR_INVALID, "medium %u: unknown phase function %u", k, m.phase);
+        if (m.phase == MI_PHASE_HG && !(m.g > -1.f && m.g < 1.f)) return fail(c, MI_ERR_INVALID, "medium %u: The asymmetry parameter must lie in the interval (-1, 1)! (g = %g)", k, (double) m.g);
+    }
+    if (s->shape_media)
+        for (uint32_t i = 0; i < 2u * s->shape_count; ++i)
+            if (s->shape_media[i] > s->media_count)
+                return fail(c, MI_ERR_INVALID, "shape %u: %s medium %u out of range (%u media; a reference is index + 1)", i / 2u, (i & 1u) ? "exterior" : "interior", s->shape_media[i], s->media_count);
+#if MIW_SPECTRAL
+    if (s->media_count) return fail(c, MI_ERR_INVALID, "scene: media are served by the scalar_rgb library");
+#endif
+    c->media.clear(); c->shape_media.clear(); c->start_medium = s->start_medium;
+    for (uint32_t k = 0; k < s->media_count; ++k) {
+        const mi_medium &m = s->media[k];
+        MediumRec r; memset(&r, 0, sizeof r);
+        for (int a = 0; a < 3; ++a) { r.sigma_t[a] = m.sigma_t[a]; r.albedo[a] = m.albedo[a]; }
+        r.has_spectral_extinction = m.has_spectral_extinction ? 1u : 0u; r.sample_emitters = m.sample_emitters ? 1u : 0u;
+        r.phase = m.phase; r.g = m.g;
+        c->media.push_back(r);
+    }
+    if (s->shape_media) c->shape_media.assign(s->shape_media, s->shape_media + 2u * (size_t) s->shape_count);
 
     // Scene::m_emitters order: the environment map and the lights sit at their emitter_index, the area emitters fill the other slots in order
     if (s->light_count && !s->lights) return fail(c, MI_ERR_INVALID, "scene: light_count without lights");
@@ -727,6 +774,8 @@ mi_status mi_scene_upload(mi_ctx *c, const mi_scene_desc *s) {
     HIP_TRY(c, c->d_bsdfs.upload(c->bsdfs, c->stream));
     HIP_TRY(c, c->d_emitters.upload(c->emitters, c->stream));
     HIP_TRY(c, c->d_lights.upload(c->lights, c->stream));
+    HIP_TRY(c, c->d_media.upload(c->media, c->stream));
+    HIP_TRY(c, c->d_shape_media.upload(c->shape_media, c->stream));
     HIP_TRY(c, c->d_emit_tri.upload(c->emit_tri, c->stream));
     HIP_TRY(c, c->d_emit_vnorm.upload(c->emit_vnorm, c->stream));
     HIP_TRY(c, c->d_emit_pmf.upload(c->emit_pmf, c->stream));
@@ -1293,7 +1342,9 @@ static mi_status fill_params(mi_ctx *c, const mi_render_cfg *cfg, RenderParams &
         if (ne + nb == 0) return fail(c, MI_ERR_INVALID, "Must have at least 1 BSDF or emitter sample!");
         P.integrator = INTEG_DIRECT;
         direct_constants(P.direct, ne, nb, cfg->hide_emitters != 0);
-    } else if (cfg->integrator != MI_INTEGRATOR_PATH)
+    } else if (cfg->integrator == MI_INTEGRATOR_VOLPATH)
+        return fail(c, MI_ERR_INVALID, "render: volpath renders through mi_render_sensor");
+    else if (cfg->integrator != MI_INTEGRATOR_PATH)
         return fail(c, MI_ERR_INVALID, "render: unknown integrator %d", cfg->integrator);
     if (cfg->moment_pass < MI_MOMENT_OFF || cfg->moment_pass > MI_MOMENT_SQUARES) return fail(c, MI_ERR_INVALID, "render: moment_pass must be 0, 1 or 2");
 #if MIW_SPECTRAL
@@ -1367,7 +1418,48 @@ static bool tree8_on(const mi_ctx *c, const Options &opt) { return c->view.nodes
 // (and the queue's 32-bit counter never wraps).
 #define MIW_SAMPLE_CHUNK_HOST (1u << 21)
 #define MIW_SAMPLE_CHUNK_DEVICE (1u << 26)
+#if !MIW_SPECTRAL
+static MediaView media_view(const mi_ctx *c) {
+    MediaView mv;
+    mv.media = c->media.empty() ? nullptr : c->d_media.p; mv.media_count = (uint32_t) c->media.size();
+    mv.shape_media = c->shape_media.empty() ? nullptr : c->d_shape_media.p; mv.start_medium = c->start_medium;
+    return mv;
+}
+// MI_INTEGRATOR_VOLPATH: k_sample_volpath (device/volpath_kernel.h) of the MATS_NESTED class, which holds every BSDF plugin; packets or
+// the tree as the scene was built. Scenes of the two routes no float64 tier pins yet are refused by name.
+static mi_status volpath_sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO &io, hipStream_t s) {
+    if (c->lights_on) return fail(c, MI_ERR_INVALID, "volpath: scenes with point / spot / directional / constant emitters are not served yet");
+    if (!c->rects.empty()) return fail(c, MI_ERR_INVALID, "volpath: scenes with analytic shapes (rectangle, sphere) are not served yet");
+    const bool tiny = c->lds_cfg.brute != 0;
+    const dim3 grid(std::min<unsigned>((io.n + MIW_BLOCK - 1u) / MIW_BLOCK, (unsigned) c->cu_count * volpath_waves(tiny ? 1 : 0)));
+    HIP_TRY(c, hipMemsetAsync(c->d_next_ray.p, 0, sizeof(uint32_t), s));
+    const MediaView mv = media_view(c);
+    const int mats = MATS_NESTED;
+    const hipError_t e = volpath_launch(s, c->opt.get("MIW_DEBUG") != nullptr, tiny ? 1 : 0, mats, false, grid, c->lds_bytes, P, c->view, mv, io, c->lds_cfg,
+                                        c->d_next_ray.p, c->d_volpath_capped.p);
+    if (e == hipErrorInvalidValue) return fail(c, MI_ERR_STATE, "mi_sample: no k_sample_volpath<%d, %d, 0> in the library", tiny ? 1 : 0, mats);
+    HIP_TRY(c, e);
+    return MI_OK;
+}
+// the counter of rays ended by MIW_VOLPATH_MAX_TRIPS: cleared before the launches of a call, read into mi_counters after them
+static mi_status volpath_capped_reset(mi_ctx *c, hipStream_t s) {
+    HIP_TRY(c, c->d_volpath_capped.resize(1));
+    HIP_TRY(c, hipMemsetAsync(c->d_volpath_capped.p, 0, sizeof(uint32_t), s));
+    c->volpath_capped = 0;
+    return MI_OK;
+}
+static mi_status volpath_capped_read(mi_ctx *c, hipStream_t s) {
+    uint32_t n = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n, c->d_volpath_capped.p, sizeof n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->volpath_capped = n;
+    return MI_OK;
+}
+#endif
 static mi_status sample_launch(mi_ctx *c, const RenderParams &P, const SampleIO &io, hipStream_t s) {
+#if !MIW_SPECTRAL
+    if (P.integrator == INTEG_VOLPATH) return volpath_sample_launch(c, P, io, s);
+#endif
     const bool tiny = c->lds_cfg.brute != 0, direct = P.integrator == INTEG_DIRECT;
     // persistent grid: as many workgroups per CU as the kernel is compiled for wavefronts per SIMD (sample_kernel.h), never more than the rays need
     const unsigned waves = direct ? (unsigned) MIW_DIRECT_WAVES : tiny ? 4u : (unsigned) MIW_TREE_WAVES;
@@ -1396,8 +1488,15 @@ static std::string sample_cfg_problem(const mi_sample_cfg *cfg) {
         if (cfg->max_depth < -1) return "\"max_depth\" must be set to -1 (infinite) or a value >= 0";
     } else if (cfg->integrator == MI_INTEGRATOR_DIRECT) {
         if (cfg->emitter_samples + cfg->bsdf_samples == 0) return "Must have at least 1 BSDF or emitter sample!";
+    } else if (cfg->integrator == MI_INTEGRATOR_VOLPATH) {
+#if MIW_SPECTRAL
+        return "volpath is served by the scalar_rgb library";
+#else
+        if (cfg->rr_depth <= 0) return "\"rr_depth\" must be set to a value greater than zero!";
+        if (cfg->max_depth < -1) return "\"max_depth\" must be set to -1 (infinite) or a value >= 0";
+#endif
     } else {
-        snprintf(buf, sizeof buf, "mi_sample: unknown integrator %d (served: MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT)", cfg->integrator);
+        snprintf(buf, sizeof buf, "mi_sample: unknown integrator %d (served: MI_INTEGRATOR_PATH, MI_INTEGRATOR_DIRECT, MI_INTEGRATOR_VOLPATH)", cfg->integrator);
         return buf;
     }
     return std::string();
@@ -1420,6 +1519,8 @@ mi_status mi_sample(mi_ctx *c, const mi_sample_cfg *cfg, const mi_rays_soa *rays
         P.integrator = INTEG_DIRECT;
         direct_constants(P.direct, cfg->emitter_samples, cfg->bsdf_samples, cfg->hide_emitters != 0);
     }
+    const bool volpath = cfg->integrator == MI_INTEGRATOR_VOLPATH;
+    if (volpath) { P.integrator = INTEG_VOLPATH; P.direct.hide_emitters = cfg->hide_emitters != 0 ? 1u : 0u; }
     if (MIW_SPECTRAL && !wavelengths) return fail(c, MI_ERR_INVALID, "mi_sample: the scalar_spectral library needs wavelengths");
     const float *src[8] = { rays->ox, rays->oy, rays->oz, rays->dx, rays->dy, rays->dz, rays->mint, rays->maxt };
     for (int k = 0; k < 8; ++k) if (!src[k]) return fail(c, MI_ERR_INVALID, "mi_sample: null ray array");
@@ -1428,6 +1529,9 @@ mi_status mi_sample(mi_ctx *c, const mi_sample_cfg *cfg, const mi_rays_soa *rays
     hipStream_t s = c->stream;
     c->cancel.store(0);
     HIP_TRY(c, c->d_next_ray.resize(1));
+#if !MIW_SPECTRAL
+    if (volpath) MI_TRY(volpath_capped_reset(c, s));
+#endif
     const bool dev = cfg->on_device != 0;
     const uint64_t chunk = dev ? MIW_SAMPLE_CHUNK_DEVICE : MIW_SAMPLE_CHUNK_HOST;
     // staged chunk of a host-pointer call: [8 ray arrays][wavelengths][rng state][rng inc][spec][valid], every array 16-byte aligned
@@ -1473,6 +1577,9 @@ mi_status mi_sample(mi_ctx *c, const mi_sample_cfg *cfg, const mi_rays_soa *rays
         }
         HIP_TRY(c, hipStreamSynchronize(s));
     }
+#if !MIW_SPECTRAL
+    if (volpath) MI_TRY(volpath_capped_read(c, s));
+#endif
     return MI_OK;
 }
 
@@ -2746,11 +2853,37 @@ mi_status mi_eval(mi_ctx *c, int32_t op, const mi_render_cfg *cfg, const float *
     }
     if ((op == MI_EVAL_BSDF || op == MI_EVAL_EMITTER_SAMPLE || op == MI_EVAL_ENVMAP || op == MI_EVAL_TEXTURE) && !c->have_bvh)
         return fail(c, MI_ERR_STATE, "mi_eval: scene required");
+    const bool medium_op = op == MI_EVAL_MEDIUM || op == MI_EVAL_PHASE;
+    if (medium_op) {
+#if MIW_SPECTRAL
+        return fail(c, MI_ERR_INVALID, "mi_eval: media are served by the scalar_rgb library");
+#else
+        if (!c->have_scene) return fail(c, MI_ERR_STATE, "mi_eval: scene required");
+        if (is < (op == MI_EVAL_MEDIUM ? 12 : 9) || os < (op == MI_EVAL_MEDIUM ? 22 : 5)) return fail(c, MI_ERR_INVALID, "mi_eval: strides too small for op %d", op);
+        for (uint64_t i = 0; i < n; ++i) {
+            const float m = in[i * (uint64_t) is];
+            if (!(m >= 0.f && m < (float) c->media.size()) || m != (float) (uint32_t) m)
+                return fail(c, MI_ERR_INVALID, "mi_eval: entry %llu: medium %g out of range (%zu media)", (unsigned long long) i, (double) m, c->media.size());
+            if (op == MI_EVAL_MEDIUM) {
+                const float ch = in[i * (uint64_t) is + 10];
+                if (!(ch == 0.f || ch == 1.f || ch == 2.f)) return fail(c, MI_ERR_INVALID, "mi_eval: entry %llu: channel %g must be 0, 1 or 2", (unsigned long long) i, (double) ch);
+            }
+        }
+#endif
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     TmpBuf<float> din, dout;
     HIP_TRY(c, din.resize(n * is)); HIP_TRY(c, dout.resize(n * os));
     HIP_TRY(c, hipMemcpyAsync(din.p, in, n * is * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(dout.p, 0, n * os * sizeof(float), c->stream));
+#if !MIW_SPECTRAL
+    if (medium_op) {
+        HIP_TRY(c, volpath_launch_eval(c->stream, op, media_view(c), din.p, is, dout.p, os, n));
+        HIP_TRY(c, hipMemcpyAsync(out, dout.p, n * os * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return MI_OK;
+    }
+#endif
     hipLaunchKernelGGL(k_eval, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, c->stream, op, P, c->view, din.p, is, dout.p, os, n);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, dout.p, n * os * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -73,9 +73,17 @@ mi_status mi_render_sensor(mi_ctx *c, const mi_render_cfg *cfg, const mi_sensor_
         if (!why.empty()) return fail(c, MI_ERR_INVALID, "mi_render_sensor: %s", why.c_str());
         PC.spp = 1u; PC.max_depth = sc.max_depth; PC.rr_depth = sc.rr_depth;
         if (sc.integrator == MI_INTEGRATOR_DIRECT) { PC.integrator = INTEG_DIRECT; direct_constants(PC.direct, sc.emitter_samples, sc.bsdf_samples, sc.hide_emitters != 0); }
+#if !MIW_SPECTRAL
+        if (sc.integrator == MI_INTEGRATOR_VOLPATH) { PC.integrator = INTEG_VOLPATH; PC.direct.hide_emitters = sc.hide_emitters != 0 ? 1u : 0u; }
+#endif
     }
+    const bool volpath = cfg->integrator == MI_INTEGRATOR_VOLPATH;
     RenderParams P;                                              // camera, film and filter (k_init_pixels, the film launches)
-    MI_TRY(fill_params(c, cfg, P));
+    {   // (the camera and film fields are the integrator's all the same: volpath's child is described above)
+        mi_render_cfg camera = *cfg;
+        if (volpath) camera.integrator = MI_INTEGRATOR_PATH;
+        MI_TRY(fill_params(c, &camera, P));
+    }
     const uint32_t bs = (uint32_t) cfg->block_size, bs2 = bs * bs;
     uint32_t bs2_log2 = 0; while ((1u << bs2_log2) < bs2) ++bs2_log2;
     const uint32_t blocks_x = (cfg->crop_w + bs - 1) / bs, blocks_y = (cfg->crop_h + bs - 1) / bs, n_tiles = blocks_x * blocks_y;
@@ -109,6 +117,9 @@ mi_status mi_render_sensor(mi_ctx *c, const mi_render_cfg *cfg, const mi_sensor_
     HIP_TRY(c, d_valid.resize(group_lanes)); HIP_TRY(c, d_rng.resize(group_lanes));
     if (MIW_SPECTRAL) { HIP_TRY(c, d_wl.resize(group_lanes)); HIP_TRY(c, d_weight.resize(group_lanes)); }
     HIP_TRY(c, c->d_next_ray.resize(1));
+#if !MIW_SPECTRAL
+    if (volpath) MI_TRY(volpath_capped_reset(c, s));
+#endif
     std::vector<int32_t> block_tile(n_tiles);
     for (uint32_t t = 0; t < n_tiles; ++t) block_tile[t] = (int32_t) t;
     HIP_TRY(c, hipMemcpyAsync(d_block_ids.p, cfg->block_ids, n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -198,6 +209,9 @@ mi_status mi_render_sensor(mi_ctx *c, const mi_render_cfg *cfg, const mi_sensor_
     HIP_TRY(c, hipStreamSynchronize(s));
     mi_counters &K = c->counters;
     K.samples = (uint64_t) cfg->crop_w * (uint64_t) cfg->crop_h * spp;
+#if !MIW_SPECTRAL
+    if (volpath) MI_TRY(volpath_capped_read(c, s));
+#endif
     if (prof) {
         add_ms(ms_merge, m0, m1);
         K.ms_path = ms_rounds; K.ms_init = ms_step; K.ms_film_blocks = ms_film; K.ms_film_merge = ms_merge; K.ms_resolve = ms_film + ms_merge;

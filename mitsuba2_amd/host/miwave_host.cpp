@@ -19,6 +19,7 @@
 #include "../csrc/miw/aov.h"
 #include "../csrc/miw/film_gather_n.h"
 #include "../csrc/miw/lens.h"
+#include "../csrc/miw/medium.h"
 #include <cctype>
 
 namespace miwave {
@@ -31,6 +32,7 @@ static std::string to_lower(std::string s) { for (char &c : s) c = (char) std::t
 #include "parts/film_sensor.inl"
 #include "parts/bsdfs.inl"
 #include "parts/shapes_scene.inl"
+#include "parts/media.inl"
 #include "parts/integrators.inl"
 #include "parts/xml.inl"
 #include "parts/facade.inl"

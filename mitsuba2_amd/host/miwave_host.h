@@ -253,6 +253,7 @@ private:
 
 // ---- Sensor (src/sensors/perspective.cpp, src/librender/sensor.cpp) ------------------------
 struct Ray3f { Point3f o; Vector3f d; float mint = 0.f, maxt = 0.f; };
+class Medium;
 
 class PerspectiveCamera {
 public:
@@ -260,6 +261,9 @@ public:
                                std::shared_ptr<IndependentSampler> sampler);
     const std::shared_ptr<Film> &film() const { return m_film; }
     const std::shared_ptr<IndependentSampler> &sampler() const { return m_sampler; }
+    // Sensor::medium (endpoint.h): the medium the sensor lies in, or null
+    void set_medium(std::shared_ptr<Medium> m) { m_medium = std::move(m); }
+    const Medium *medium() const { return m_medium.get(); }
     float near_clip() const { return m_near_clip; }
     float far_clip() const { return m_far_clip; }
     float x_fov() const { return m_x_fov; }
@@ -287,6 +291,7 @@ protected:
     float m_shutter_open = 0.f, m_shutter_open_time = 0.f;     // read by ThinLensCamera alone
 private:
     void update_camera_transforms();                           // :118-141
+    std::shared_ptr<Medium> m_medium;
     std::shared_ptr<Film> m_film;
     std::shared_ptr<IndependentSampler> m_sampler;
     Transform4f m_to_world, m_camera_to_sample, m_sample_to_camera;
@@ -472,8 +477,61 @@ class ConstantBackgroundEmitter final : public Light { public: explicit Constant
 // the plugin of that name, or nullptr when `props` names none of the four
 std::shared_ptr<Light> make_light(const Properties &props);
 
+// ---- participating media (include/mitsuba/render/medium.h, phase.h; src/media/homogeneous.cpp, src/phase/*.cpp) ----
+class PhaseFunction {
+public:
+    virtual ~PhaseFunction() = default;
+    virtual uint32_t type() const = 0;                         // MI_PHASE_*
+    virtual float g() const { return 0.f; }
+    // PhaseFunction::sample(ctx, mi, sample) / eval(ctx, mi, wo) for mi.wi = -ray_d, mi.sh_frame = Frame3f(ray_d): the host compile of
+    // the device's leaves (csrc/miw/medium.h)
+    std::pair<Vector3f, float> sample(const Vector3f &ray_d, const std::array<float, 2> &sample) const;
+    float eval(const Vector3f &ray_d, const Vector3f &wo) const;
+};
+class IsotropicPhaseFunction final : public PhaseFunction {    // isotropic.cpp:27-29
+public:
+    explicit IsotropicPhaseFunction(const Properties & = Properties("isotropic")) {}
+    uint32_t type() const override { return MI_PHASE_ISOTROPIC; }
+};
+class HGPhaseFunction final : public PhaseFunction {           // hg.cpp:43-49
+public:
+    explicit HGPhaseFunction(const Properties &props);
+    uint32_t type() const override { return MI_PHASE_HG; }
+    float g() const override { return m_g; }
+private:
+    float m_g;
+};
+std::shared_ptr<PhaseFunction> make_phase(const Properties &props);   // "isotropic" | "hg"
+// Medium (medium.cpp:9-30) and HomogeneousMedium (homogeneous.cpp:21-28) with constant sigma_t / albedo volumes
+class Medium {
+public:
+    Medium(const Properties &props, std::shared_ptr<PhaseFunction> phase);
+    virtual ~Medium() = default;
+    const PhaseFunction *phase_function() const { return m_phase_function.get(); }
+    bool use_emitter_sampling() const { return m_sample_emitters; }
+    bool is_homogeneous() const { return m_is_homogeneous; }
+    bool has_spectral_extinction() const { return m_has_spectral_extinction; }
+    virtual mi_medium record() const = 0;                      // the flat record mi_scene_upload takes
+protected:
+    std::shared_ptr<PhaseFunction> m_phase_function;
+    bool m_sample_emitters, m_is_homogeneous = false, m_has_spectral_extinction = true;
+};
+class HomogeneousMedium final : public Medium {
+public:
+    explicit HomogeneousMedium(const Properties &props, std::shared_ptr<PhaseFunction> phase = nullptr);
+    mi_medium record() const override;
+private:
+    Color3f m_sigmat, m_albedo; float m_scale;
+};
+
 class Mesh {                                                  // include/mitsuba/render/mesh.h
 public:
+    // Shape::interior_medium / exterior_medium / is_medium_transition (shape.h:341-348)
+    void set_interior_medium(std::shared_ptr<Medium> m) { m_interior_medium = std::move(m); }
+    void set_exterior_medium(std::shared_ptr<Medium> m) { m_exterior_medium = std::move(m); }
+    const Medium *interior_medium() const { return m_interior_medium.get(); }
+    const Medium *exterior_medium() const { return m_exterior_medium.get(); }
+    bool is_medium_transition() const { return m_interior_medium || m_exterior_medium; }
     Mesh(std::string name, std::vector<float> vertex_positions, std::vector<uint32_t> faces,
          std::vector<float> vertex_normals = {}, std::vector<float> vertex_texcoords = {});
     uint32_t vertex_count() const { return (uint32_t) (m_positions.size() / 3); }
@@ -515,6 +573,7 @@ private:
     std::vector<uint32_t> m_faces;
     std::shared_ptr<BSDF> m_bsdf;
     std::shared_ptr<AreaLight> m_emitter;
+    std::shared_ptr<Medium> m_interior_medium, m_exterior_medium;
     bool m_rectangle = false; Transform4f m_rect_to_world;
     bool m_sphere = false; mi_sphere m_sphere_rec{};
 };
@@ -546,6 +605,10 @@ public:
     // emitter order after the shapes added so far; a constant emitter is an environment emitter (one per scene)
     void add_emitter(std::shared_ptr<Light> light);
     const EnvironmentMapEmitter *environment() const { return m_env.get(); }   // scene.h:150-151
+    // the medium the scene's sensor lies in (Sensor::medium): mi_scene_desc::start_medium. The description carries it because the
+    // rays of SamplingIntegrator::sample start in it too; render() checks that the sensor it is handed names the same medium.
+    void set_start_medium(std::shared_ptr<Medium> m) { m_start_medium = std::move(m); }
+    const Medium *start_medium() const { return m_start_medium.get(); }
     // finishes construction: default BSDFs (shape.cpp:75-81), flatten, upload, build accel (scene.cpp:94-97)
     void build(int device = 0, int bvh_quality = 0);   // 0: the binned-SAH tree built on the device (csrc/sah_device.h), 1: by the host recursion
     // The same scene resident on SEVERAL GPUs of the node (round 5): one context per entry of `devices` (devices[0] = the primary,
@@ -589,6 +652,7 @@ private:
     std::shared_ptr<EnvironmentMapEmitter> m_env; size_t m_env_after_shapes = 0; mi_envmap m_env_rec{};
     struct LightChild { std::shared_ptr<Light> light; size_t after_shapes, seq; };
     std::vector<LightChild> m_lights; size_t m_env_seq = 0, m_child_seq = 0; std::vector<mi_light> m_light_recs;
+    std::shared_ptr<Medium> m_start_medium; std::vector<const Medium *> m_media; std::vector<mi_medium> m_medium_recs; std::vector<uint32_t> m_shape_media;
     mi_scene_desc m_desc{};
     mi_ctx *m_ctx = nullptr;
     std::vector<mi_ctx *> m_replicas;                          // the contexts of devices[1..] of a multi-GPU build
@@ -627,6 +691,8 @@ public:
                          uint32_t n_threads_hint, uint32_t pass, uint32_t rank, uint32_t world) const;
     uint32_t pass_count(const PerspectiveCamera *sensor) const;
     const mi_counters &counters() const { return m_counters; }
+    // volpath: rays of the last render() through the sensor route that the lane loop's trip bound ended (mi_volpath_capped), summed over its passes
+    uint64_t volpath_capped() const { return m_volpath_capped; }
     void set_profile(bool p) { m_profile = p; }
     // execution plan of the device sample loop (mi_render_cfg::plan): 0 auto, 1 wavefront, 2 resident
     void set_plan(int plan) { m_plan = plan; }
@@ -656,6 +722,7 @@ protected:
     int m_plan = 0;
     std::atomic<mi_ctx *> m_active_ctx{nullptr};
     mi_counters m_counters{};
+    uint64_t m_volpath_capped = 0;
 };
 
 // src/integrators/path.cpp (MonteCarloIntegrator parameters, integrator.cpp:305-314)
@@ -664,6 +731,20 @@ public:
     explicit PathIntegrator(const Properties &props = Properties("path"));
     int max_depth() const { return m_max_depth; }
     int rr_depth() const { return m_rr_depth; }
+protected:
+    void fill_integrator(mi_render_cfg &cfg) const override;
+private:
+    int m_max_depth, m_rr_depth;
+};
+
+// src/integrators/volpath.cpp (MonteCarloIntegrator parameters + hide_emitters): sample() runs on the device (mi_sample); render()
+// goes through the general sensor route (mi_render_sensor), one device, no tile shards
+class VolumetricPathIntegrator final : public SamplingIntegrator {
+public:
+    explicit VolumetricPathIntegrator(const Properties &props = Properties("volpath"));
+    int max_depth() const { return m_max_depth; }
+    int rr_depth() const { return m_rr_depth; }
+    bool render(Scene *scene, PerspectiveCamera *sensor) override;
 protected:
     void fill_integrator(mi_render_cfg &cfg) const override;
 private:

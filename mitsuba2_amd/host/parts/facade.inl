@@ -440,6 +440,56 @@ int mih_sensor_sample_rays(void *s, const float *position, const float *aperture
 int mih_sensor_desc(void *s, mi_sensor_desc *out) { MIH_TRY *out = ((Box<PerspectiveCamera> *) s)->p->desc(); return 0; MIH_CATCH(-1) }
 int mih_sensor_needs_aperture_sample(void *s) { return ((Box<PerspectiveCamera> *) s)->p->needs_aperture_sample() ? 1 : 0; }
 
+// ---- participating media ----
+void *mih_phase_create(void *props) { MIH_TRY return new Box<PhaseFunction>{ make_phase(*(Properties *) props) }; MIH_CATCH(nullptr) }
+void mih_phase_destroy(void *p) { delete (Box<PhaseFunction> *) p; }
+// PhaseFunction::sample / eval for a medium interaction of a ray with direction ray_d: out = wo.xyz, pdf, eval(wo_eval)
+int mih_phase_sample_eval(void *p, const float *ray_d, const float *sample2, const float *wo_eval, float *out5) {
+    MIH_TRY const PhaseFunction &f = *((Box<PhaseFunction> *) p)->p;
+        auto r = f.sample({ ray_d[0], ray_d[1], ray_d[2] }, { sample2[0], sample2[1] });
+        out5[0] = r.first[0]; out5[1] = r.first[1]; out5[2] = r.first[2]; out5[3] = r.second;
+        out5[4] = f.eval({ ray_d[0], ray_d[1], ray_d[2] }, { wo_eval[0], wo_eval[1], wo_eval[2] }); return 0; MIH_CATCH(-1)
+}
+// <medium type="homogeneous"> with an optional phase function child (NULL: isotropic, medium.cpp:23-27)
+void *mih_medium_create(void *props, void *phase) {
+    MIH_TRY
+        const Properties &p = *(Properties *) props;
+        if (p.plugin_name() != "homogeneous") throw std::runtime_error("Plugin \"" + p.plugin_name() + "\" not found!");
+        return new Box<Medium>{ std::make_shared<HomogeneousMedium>(p, phase ? ((Box<PhaseFunction> *) phase)->p : nullptr) }; MIH_CATCH(nullptr)
+}
+void mih_medium_destroy(void *m) { delete (Box<Medium> *) m; }
+int mih_medium_record(void *m, mi_medium *out) { MIH_TRY *out = ((Box<Medium> *) m)->p->record(); return 0; MIH_CATCH(-1) }
+// Medium::sample_interaction(ray, sample, channel) and eval_tr_and_pdf(mi, si) with si.t = si_t, through the host compile of the device's
+// leaves. ray8 = o.xyz d.xyz mint maxt. out18 = t, mint, p.xyz, sigma_s[3], sigma_t[3], combined_extinction[3], sampled_t; tr_pdf6 = tr[3], pdf[3]
+int mih_medium_sample_interaction(void *m, const float *ray8, float sample, uint32_t channel, float si_t, float *out16, float *tr_pdf6) {
+    MIH_TRY
+#if MIW_SPECTRAL
+        throw std::runtime_error("media are served by the scalar_rgb library");
+#else
+        const mi_medium r = ((Box<Medium> *) m)->p->record();
+        miw::MediumRec q; std::memcpy(&q, &r, sizeof q);
+        miw::Ray ray; ray.o = miw::v3(ray8[0], ray8[1], ray8[2]); ray.d = miw::v3(ray8[3], ray8[4], ray8[5]); ray.mint = ray8[6]; ray.maxt = ray8[7];
+        const miw::MediumInteraction mi = miw::medium_sample_interaction(q, ray, sample, channel);
+        out16[0] = mi.t; out16[1] = mi.mint; out16[2] = mi.p.x; out16[3] = mi.p.y; out16[4] = mi.p.z;
+        out16[5] = mi.sigma_s.x; out16[6] = mi.sigma_s.y; out16[7] = mi.sigma_s.z;
+        out16[8] = mi.sigma_t.x; out16[9] = mi.sigma_t.y; out16[10] = mi.sigma_t.z;
+        out16[11] = mi.sigma_t.x; out16[12] = mi.sigma_t.y; out16[13] = mi.sigma_t.z; out16[14] = mi.ts; out16[15] = 0.f;
+        miw::Spec tr, pdf;
+        miw::MediumInteraction m2 = mi; if (si_t < m2.t) m2.t = MIW_INFINITY;       // volpath.cpp:112
+        miw::medium_eval_tr_and_pdf(m2, si_t, tr, pdf);
+        tr_pdf6[0] = tr.x; tr_pdf6[1] = tr.y; tr_pdf6[2] = tr.z; tr_pdf6[3] = pdf.x; tr_pdf6[4] = pdf.y; tr_pdf6[5] = pdf.z;
+        return 0;
+#endif
+    MIH_CATCH(-1)
+}
+void mih_mesh_set_media(void *m, void *interior, void *exterior) {
+    ((Box<Mesh> *) m)->p->set_interior_medium(interior ? ((Box<Medium> *) interior)->p : nullptr);
+    ((Box<Mesh> *) m)->p->set_exterior_medium(exterior ? ((Box<Medium> *) exterior)->p : nullptr);
+}
+int mih_mesh_is_medium_transition(void *m) { return ((Box<Mesh> *) m)->p->is_medium_transition() ? 1 : 0; }
+void mih_scene_set_start_medium(void *s, void *medium) { ((Box<Scene> *) s)->p->set_start_medium(medium ? ((Box<Medium> *) medium)->p : nullptr); }
+void mih_sensor_set_medium(void *s, void *medium) { ((Box<PerspectiveCamera> *) s)->p->set_medium(medium ? ((Box<Medium> *) medium)->p : nullptr); }
+
 void *mih_integrator_create(void *props) {
     MIH_TRY
         const Properties &p = *(Properties *) props;
@@ -502,6 +552,7 @@ int mih_integrator_sample_batch(void *i, void *scene, const mi_rays_soa *rays, c
 }
 int mih_integrator_sample_cfg(void *i, mi_sample_cfg *cfg) { MIH_TRY ((Box<SamplingIntegrator> *) i)->p->fill_sample_cfg(*cfg); return 0; MIH_CATCH(-1) }
 int mih_integrator_last_reduce(void *i) { return ((Box<SamplingIntegrator> *) i)->p->last_reduce(); }
+uint64_t mih_integrator_volpath_capped(void *i) { return ((Box<SamplingIntegrator> *) i)->p->volpath_capped(); }
 int mih_integrator_counters(void *i, mi_counters *out) { *out = ((Box<SamplingIntegrator> *) i)->p->counters(); return 0; }
 // Host-side job description (no GPU needed). block_ids / tiles must hold `capacity` entries.
 int mih_make_render_cfg(void *i, void *sensor, mi_render_cfg *cfg, uint32_t *block_ids, uint32_t *tiles, uint32_t capacity, uint32_t n_threads) {

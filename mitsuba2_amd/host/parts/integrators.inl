@@ -36,11 +36,26 @@ void DirectIntegrator::fill_integrator(mi_render_cfg &cfg) const {
     cfg.emitter_samples = (uint32_t) m_emitter_samples; cfg.bsdf_samples = (uint32_t) m_bsdf_samples;
     cfg.hide_emitters = m_hide_emitters ? 1 : 0;
 }
+// volpath.cpp:48 (MonteCarloIntegrator, integrator.cpp:305-314)
+VolumetricPathIntegrator::VolumetricPathIntegrator(const Properties &props) : SamplingIntegrator(props) {
+    m_rr_depth = (int) props.int_("rr_depth", 5);
+    if (m_rr_depth <= 0) Throw("\"rr_depth\" must be set to a value greater than zero!");
+    m_max_depth = (int) props.int_("max_depth", -1);
+    if (m_max_depth < 0 && m_max_depth != -1) Throw("\"max_depth\" must be set to -1 (infinite) or a value >= 0");
+#if MIW_SPECTRAL
+    Throw("volpath is served by the scalar_rgb library");
+#endif
+}
+void VolumetricPathIntegrator::fill_integrator(mi_render_cfg &cfg) const {
+    cfg.integrator = MI_INTEGRATOR_VOLPATH; cfg.max_depth = m_max_depth; cfg.rr_depth = m_rr_depth;
+    cfg.hide_emitters = m_hide_emitters ? 1 : 0;
+}
 std::shared_ptr<SamplingIntegrator> make_integrator(const Properties &props) {
     if (props.plugin_name() == "moment") Throw("moment: needs a nested integrator (MomentIntegrator(props, nested))");
     if (props.plugin_name() == "aov") return std::make_shared<AOVIntegrator>(props);
     if (props.plugin_name() == "path") return std::make_shared<PathIntegrator>(props);
     if (props.plugin_name() == "direct") return std::make_shared<DirectIntegrator>(props);
+    if (props.plugin_name() == "volpath") return std::make_shared<VolumetricPathIntegrator>(props);
     Throw("Plugin \"" + props.plugin_name() + "\" not found!");
 }
 void SamplingIntegrator::cancel() {
@@ -227,6 +242,7 @@ bool SamplingIntegrator::render_sensor_passes(Scene *scene, PerspectiveCamera *s
     const uint32_t passes = pass_count(sensor);
     mi_counters total{};
     m_last_reduce = MI_REDUCE_NONE;
+    m_volpath_capped = 0;
     for (uint32_t pass = 0; pass < passes; ++pass) {
         mi_render_cfg cfg; std::vector<uint32_t> block_ids, tiles;
         make_render_cfg(sensor, cfg, block_ids, tiles, 1, pass);
@@ -234,6 +250,7 @@ bool SamplingIntegrator::render_sensor_passes(Scene *scene, PerspectiveCamera *s
         mi_status st = mi_render_sensor(scene->ctx(), &cfg, &desc, film5);
         m_active_ctx.store(nullptr);
         mi_get_counters(scene->ctx(), &m_counters);
+        if (cfg.integrator == MI_INTEGRATOR_VOLPATH) { uint64_t capped = 0; if (mi_volpath_capped(scene->ctx(), &capped) == MI_OK) m_volpath_capped += capped; }
         if (pass > 0) { m_counters.samples += total.samples; m_counters.ms_render += total.ms_render; }
         total = m_counters;
         if (st == MI_ERR_CANCELLED) return false;
@@ -248,6 +265,17 @@ bool SamplingIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
     film->prepare({ "X", "Y", "Z", "A", "W" });                // integrator.cpp:67-73
     if (sensor->is_thinlens()) return render_sensor_passes(scene, sensor, film->storage().data());
     return render_passes(scene, sensor, film->storage().data(), MI_MOMENT_OFF);
+}
+
+// volpath's frames: the general sensor route for every sensor (its sample() has no resident-plan kernel)
+bool VolumetricPathIntegrator::render(Scene *scene, PerspectiveCamera *sensor) {
+    if (!scene || !sensor) Throw("render(): null scene or sensor");
+    if (!scene->ctx()) Throw("render(): the scene has no device context (Scene::build(device >= 0) first)");
+    if (sensor->medium() != scene->start_medium())
+        Throw("volpath: the sensor's medium is not the medium the scene was built with (Scene::set_start_medium): rays would start in another medium");
+    Film *film = sensor->film().get();
+    film->prepare({ "X", "Y", "Z", "A", "W" });                // integrator.cpp:67-73
+    return render_sensor_passes(scene, sensor, film->storage().data());
 }
 
 // SamplingIntegrator::sample (integrator.h:114-119) through mi_sample
@@ -283,6 +311,7 @@ MomentIntegrator::MomentIntegrator(const Properties &props, std::shared_ptr<Samp
     : SamplingIntegrator(props), m_nested(std::move(nested)), m_name(std::move(nested_name)) {
     if (!m_nested) Throw("Child objects must be of type 'SamplingIntegrator'!");
     if (dynamic_cast<MomentIntegrator *>(m_nested.get())) Throw("moment: nested moment integrators are not supported");
+    if (dynamic_cast<VolumetricPathIntegrator *>(m_nested.get())) Throw("moment: a nested volpath integrator is not served (volpath renders through mi_render_sensor)");
 #if MIW_SPECTRAL
     Throw("moment: provided by the scalar_rgb build of this layer only");
 #endif
@@ -340,6 +369,8 @@ static std::vector<std::string> tokenize(const std::string &str, const std::stri
 }
 // aov.cpp:83-154
 AOVIntegrator::AOVIntegrator(const Properties &props, std::vector<Child> children) : SamplingIntegrator(props) {
+    for (const Child &ch : children)
+        if (dynamic_cast<VolumetricPathIntegrator *>(ch.second.get())) Throw("aov: a nested volpath integrator is not served (volpath renders through mi_render_sensor)");
     static const struct { const char *name; uint8_t type; const char *suffix[3]; } table[] = {
         { "depth", MI_AOV_DEPTH, { "", nullptr, nullptr } }, { "position", MI_AOV_POSITION, { ".X", ".Y", ".Z" } },
         { "uv", MI_AOV_UV, { ".U", ".V", nullptr } }, { "geo_normal", MI_AOV_GEO_NORMAL, { ".X", ".Y", ".Z" } },

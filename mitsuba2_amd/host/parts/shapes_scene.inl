@@ -521,6 +521,18 @@ void Scene::build(int device, int bvh_quality) {
         m_light_recs.push_back(r);
     }
     m_desc.lights = m_light_recs.empty() ? nullptr : m_light_recs.data(); m_desc.light_count = (uint32_t) m_light_recs.size();
+    // participating media: every distinct Medium the sensor or a shape names, in the order met; references are index + 1, 0 = none
+    m_media.clear(); m_medium_recs.clear(); m_shape_media.clear();
+    auto medium_ref = [this](const Medium *m) -> uint32_t {
+        if (!m) return 0u;
+        auto it = std::find(m_media.begin(), m_media.end(), m);
+        if (it == m_media.end()) { m_media.push_back(m); m_medium_recs.push_back(m->record()); return (uint32_t) m_media.size(); }
+        return (uint32_t) (it - m_media.begin()) + 1u;
+    };
+    m_desc.start_medium = medium_ref(m_start_medium.get());
+    for (const auto &sh : m_shapes) { m_shape_media.push_back(medium_ref(sh->interior_medium())); m_shape_media.push_back(medium_ref(sh->exterior_medium())); }
+    m_desc.media = m_medium_recs.empty() ? nullptr : m_medium_recs.data(); m_desc.media_count = (uint32_t) m_medium_recs.size();
+    m_desc.shape_media = m_medium_recs.empty() ? nullptr : m_shape_media.data();
     if (m_env) {
         if (m_env->data().empty()) Throw("envmap: no bitmap set");
         m_env_rec.rgba = m_env->data().data(); m_env_rec.width = m_env->width(); m_env_rec.height = m_env->height();

@@ -479,3 +479,59 @@ def random_triangles(n, seed=7, extent=1.0, size=0.05):
     v = (c + rng.normal(0, size, (n, 3, 3))).reshape(-1, 3).astype(np.float32)
     f = np.arange(3 * n, dtype=np.uint32).reshape(-1, 3)
     return v, f
+
+
+# ---- scenes with participating media (api.VolPathIntegrator) -----------------------------------------------------------------
+def _cube(lo, hi):
+    """an axis-aligned box as 12 triangles, normals outward"""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    quads = [[(x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0)], [(x0, y0, z1), (x1, y0, z1), (x1, y1, z1), (x0, y1, z1)],
+             [(x0, y0, z0), (x0, y0, z1), (x0, y1, z1), (x0, y1, z0)], [(x1, y0, z0), (x1, y0, z1), (x1, y1, z1), (x1, y1, z0)],
+             [(x0, y0, z0), (x1, y0, z0), (x1, y0, z1), (x0, y0, z1)], [(x0, y1, z0), (x1, y1, z0), (x1, y1, z1), (x0, y1, z1)]]
+    return _block(quads)
+
+
+def volpath_scene(which, light_drop=0.0):
+    """-> api.Scene (not built) of the volpath test scenes; every one is the Cornell room with its area light hung `light_drop` lower.
+      fog-cornell      the all-diffuse box (a packet scene), the sensor inside a fog with rgb sigma_t and isotropic phase
+      smoke-cube-gray  an empty room with a 12-triangle cube of `null` BSDF whose interior is a gray hg (g = 0.6) smoke with
+                       has_spectral_extinction = false and sample_emitters = false
+      milk-block       the glass-block box: the closed dielectric solid holds a dense hg medium (null transmission 0)
+      cornell-nomedia  the all-diffuse box without any medium
+      fog-panes        the fog-filled empty room with two panes between light and floor: mask(diffuse, opacity 0.5) and thindielectric
+      bubble-cube      a fog-filled empty room with a `null` cube whose EXTERIOR is the fog and whose interior is none"""
+    room = lambda blocks: [m for m in cornell_box_meshes(diffuse_only=True, glass_block=(which == "milk-block"))
+                           if blocks or m.name not in ("short_block", "tall_block")]
+    start = None
+    if which == "cornell-nomedia":
+        meshes = room(True)
+    elif which == "fog-cornell":
+        meshes = room(True)
+        start = api.HomogeneousMedium(sigma_t=(0.0012, 0.0016, 0.0022), albedo=(0.8, 0.85, 0.9), phase=api.IsotropicPhase())
+    elif which == "fog-panes":                                   # BSDF::eval_null_transmission of mask and thindielectric inside the shadow walks
+        meshes = room(False)
+        start = api.HomogeneousMedium(sigma_t=(0.0012, 0.0016, 0.0022), albedo=(0.8, 0.85, 0.9))
+        v, f = _quad([(100, 420, 150), (270, 420, 150), (270, 420, 400), (100, 420, 400)], inward_point=(185, 548, 275))
+        meshes.append(api.Mesh("mask_pane", v, f, bsdf=api.Mask(api.BSDF("diffuse", reflectance=WHITE), opacity=0.5)))
+        v, f = _quad([(290, 420, 150), (460, 420, 150), (460, 420, 400), (290, 420, 400)], inward_point=(375, 548, 275))
+        meshes.append(api.Mesh("thin_pane", v, f, bsdf=api.BSDF("thindielectric", int_ior=1.5046, ext_ior=1.000277)))
+    elif which == "smoke-cube-gray":
+        smoke = api.HomogeneousMedium(sigma_t=0.4, albedo=0.7, scale=0.02, phase=api.HGPhase(g=0.6), sample_emitters=False, has_spectral_extinction=False)
+        v, f = _cube((170.0, 60.0, 170.0), (390.0, 280.0, 390.0))
+        meshes = room(False) + [api.Mesh("smoke_cube", v, f, bsdf=api.BSDF("null"), interior=smoke)]
+    elif which == "milk-block":
+        milk = api.HomogeneousMedium(sigma_t=(0.02, 0.03, 0.045), albedo=(0.95, 0.9, 0.8), phase=api.HGPhase(g=0.6))
+        meshes = room(True)
+        for m in meshes:
+            if m.name == "tall_block":
+                m.set_media(interior=milk)
+    elif which == "bubble-cube":
+        start = api.HomogeneousMedium(sigma_t=(0.002, 0.0015, 0.001), albedo=0.9)
+        v, f = _cube((170.0, 60.0, 170.0), (390.0, 280.0, 390.0))
+        meshes = room(False) + [api.Mesh("bubble", v, f, bsdf=api.BSDF("null"), exterior=start)]
+    else:
+        raise KeyError(which)
+    for i, m in enumerate(meshes):
+        if m.name == "light" and light_drop:
+            meshes[i] = api.Mesh("light", m.vertices - np.array([0, light_drop, 0], np.float32), m.faces, emitter=api.AreaLight(LIGHT_RADIANCE))
+    return api.Scene(meshes, start_medium=start)
